@@ -19,11 +19,17 @@ per-frame RMSDs over RCCL (torch.distributed, backend nccl) inside the timed reg
 processes `--frames-per-step` frames per step.
 
 Prints ONE JSON line on rank 0.  `roofline` is for the dominant kernel, measured with HIP events on the
-library's own stream during the timed region (gr_profile_*); `cpu_baseline` times the CPU oracle's restatement
-of the reference path (oracle/, kind "port") on a bounded sample of the same frames, rank 0 at N=1 only -- in a fresh
-CHILD process that never touches the GPU (`bench.py --cpu-baseline-child`), so nothing on the CPU side can take the GPU
-number down with it; nproc, CPU model and both thread counts (all visible cores, and 16 = one GPU's share of the node) are
-reported as BASELINE.md section 3 promises.
+library's own stream during the timed region (gr_profile_*).  A plain run does only that: set-up, warm-up, the timed steps,
+--dump-outputs if asked, the line.  `--full` adds the measurements that take runs of their own: `cpu_baseline` times the CPU
+oracle's restatement of the reference path (oracle/, kind "port") on a bounded sample of the same frames, rank 0 at N=1 only --
+in a fresh CHILD process that never touches the GPU (`bench.py --cpu-baseline-child`), so nothing on the CPU side can take the
+GPU number down with it; nproc, CPU model and both thread counts (all visible cores, and 16 = one GPU's share of the node) are
+reported as BASELINE.md section 3 promises; and `roofline.copy_floor_live`, the arithmetic-free probe of the same launch shape.
+
+--dump-outputs DIR writes what the last timed step returned, for comparing two builds on the same (seeded) inputs:
+rmsd.npy (float32, the step's per-frame RMSDs, global frame order), status.npy (rank 0's per-frame status codes as float32) and
+fitted_positions.npy (float32, frames x atoms x 3: the fitted coordinates of a fixed seeded sample of rank 0's frames of the
+step, every atom while 4 frames fit in 48 MB, else a fixed seeded sample of atoms as well).
 """
 import argparse
 import json
@@ -58,8 +64,10 @@ def main():
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads of the CPU baseline's main figure (0 = all host cores visible "
                     "to this process); a second figure at 16 threads (one GPU's share of the node) is always reported")
     ap.add_argument("--cpu-max-frames", type=int, default=512, help="upper bound on the CPU sample (frames; 12 MB each in /dev/shm)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-live-floor", action="store_true", help="do not run the arithmetic-free copy probe (tools/bin/ceiling_resident) beside the "
+    ap.add_argument("--full", action="store_true", help="also the measurements beside the headline that take runs of their own: the CPU "
+                    "baseline and the live copy-floor probe (a plain run does only the headline)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="under --full: no CPU baseline")
+    ap.add_argument("--no-live-floor", action="store_true", help="under --full: do not run the arithmetic-free copy probe (tools/bin/copy_matrix3) beside the "
                     "result; implied under a profiler (ROCPROF* / ROCP_* variables or an LD_PRELOAD are inherited by the child)")
     ap.add_argument("--tune", action="append", default=[], metavar="KEY=VALUE", help="gr_ctx_set_tuning (sub_batch, chunks, fit_wgs, fuse, "
                     "two_pass): launch-geometry sweeps; the defaults are the measured optimum")
@@ -68,6 +76,8 @@ def main():
                     "ncclCommInitRank + ncclAllGather; the unique id travels through torch.distributed)")
     ap.add_argument("--dump-rmsd", default=None, metavar="PATH", help="rank 0 writes the per-frame RMSDs of the timed steps, in GLOBAL frame "
                     "order (after the gather at N > 1), as a .npy file: what tests/test_gpu_multirank.py compares between rank counts")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="rank 0 writes what the last timed step returned as DIR/<name>.npy "
+                    "(rmsd, status, fitted_positions: see the module docstring), at most 64 MB in all")
     ap.add_argument("--cpu-baseline-child", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--with-torch", action="store_true", help="import torch first even at N=1 (coexistence check)")
     args = ap.parse_args()
@@ -236,6 +246,9 @@ def main():
         assert np.array_equal(gathered[rank::world], rmsd_all.reshape(-1)) and np.isfinite(gathered).all()
     total_frames = K * B * world
     value = total_frames / elapsed
+    if rank == 0 and args.dump_outputs:
+        # before anything else touches the frame slots (the CPU baseline regenerates and refits the first ones)
+        dump_outputs(args.dump_outputs, rmsd_all[-1] if gathered is None else gathered[(K - 1) * B * world:], st, cur, step_slot(W + K - 1), B, n)
 
     # ---- roofline of the dominant kernel (HIP events on the library's stream, timed region)
     # `achieved` counts the bytes the kernel HAS TO MOVE through HBM per launch, every array once:
@@ -287,7 +300,7 @@ def main():
     copy_floor_live = None
     # only a profiler that is actually wrapped round this process (rocprofv3 preloads its tool library and names it in these variables)
     profiled = "rocprof" in os.environ.get("LD_PRELOAD", "") or any(k in os.environ for k in ("ROCP_TOOL_LIBRARIES", "ROCPROF_OUTPUT_PATH", "ROCPROFILER_LIBRARY_CTOR"))
-    if rank == 0 and dom == "k_fit_resident" and not args.no_live_floor and not profiled:
+    if rank == 0 and dom == "k_fit_resident" and args.full and not args.no_live_floor and not profiled:
         try:
             exe = os.path.join(ROOT, "tools", "bin", "copy_matrix3")
             if os.path.isfile(exe):
@@ -348,7 +361,7 @@ def main():
 
     # ---- CPU baseline: the oracle's restatement of the reference path on a bounded sample of the SAME frames (rank 0, N=1 only),
     # timed in a child process that never touches the GPU; a failure there is reported, never fatal for the GPU number
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         tmpdir = None
         try:
             t_main = args.cpu_threads or usable_cores()
@@ -407,6 +420,21 @@ def main():
     plan.close(); ref.close(); cur.close()
     if dist is not None:
         dist.destroy_process_group()
+
+
+def dump_outputs(out_dir, rmsd, status, cur, first_slot, n_frames, n_atoms):
+    """What the last timed step returned (see the module docstring).  The sample of frames and atoms depends on the arguments
+    only, so two builds run with the same arguments write the same frames and atoms."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "rmsd.npy"), np.asarray(rmsd, np.float32))
+    np.save(os.path.join(out_dir, "status.npy"), np.asarray(status, np.float32))
+    rng = np.random.default_rng(SEED)
+    k = min(n_frames, 4)
+    frames = np.sort(rng.choice(n_frames, k, replace=False))
+    m = min(n_atoms, (48 << 20) // (12 * k))
+    atoms = np.sort(rng.choice(n_atoms, m, replace=False)) if m < n_atoms else slice(None)
+    np.save(os.path.join(out_dir, "fitted_positions.npy"), np.stack([cur.get_positions(first_slot + int(f))[atoms] for f in frames]))
 
 
 def launch_ranks(n_ranks):

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import groan_rs_amd as G
+from test_xtc_decoder import ref_pin
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 EXP = json.load(open(os.path.join(GOLD, "trr_expected.json")))
@@ -38,14 +39,10 @@ def test_every_frame_like_the_reference_reader(name):
     t.close()
 
 
-REF_TF = "/root/reference/test_files"
-
-
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF_TF, "short_trajectory.trr")), reason="reference tree not mounted (build container only)")
 def test_known_answers_of_the_reference_tests():
-    """the values the reference pins for its 16 844-atom trajectories (src/io/trr_io.rs:574-640, 806-850); the files are too
-    large for fixtures, so this runs where the reference tree is mounted"""
-    t = G.TrrFile(os.path.join(REF_TF, "short_trajectory.trr"))
+    """the values the reference pins for its 16 844-atom trajectories (src/io/trr_io.rs:574-640, 806-850); the fixture holds the
+    first two of the nine frames of the reference's short_trajectory.trr, byte for byte (the whole file is 2.8 MB)"""
+    t = G.TrrFile(os.path.join(GOLD, "short_trajectory_first2.trr"))
     assert t.n_atoms == 16844
     x, v, f, box9, step, time, lam = t.read_frame(0, velocities=True, forces=True)
     assert step == 0 and lam == 0.0 and abs(time) < 1e-6
@@ -58,9 +55,9 @@ def test_known_answers_of_the_reference_tests():
     assert step == 6000 and abs(time - 120.0) < 1e-4
     np.testing.assert_allclose(box9[:3], [13.024242, 13.024242, 11.242146], atol=2e-6)
     t.close()
-    if not os.path.exists(os.path.join(REF_TF, "short_trajectory_double.trr")):    # (not in every checkout of the reference)
+    if not os.path.exists(os.path.join(GOLD, "short_trajectory_double.trr")):    # (not in every checkout of the reference)
         return
-    d = G.TrrFile(os.path.join(REF_TF, "short_trajectory_double.trr"))
+    d = G.TrrFile(os.path.join(GOLD, "short_trajectory_double.trr"))
     x, v, f, box9, step, time, lam = d.read_frame(0, velocities=True, forces=True)
     assert d.frame_info(0)["double_precision"] and step == 0
     np.testing.assert_allclose(x[0], [9.497161, 1.9891102, 7.497941], rtol=1e-6); np.testing.assert_allclose(v[0], [-0.06389237, 0.054320477, 0.008154817], rtol=1e-6)
@@ -106,31 +103,45 @@ def test_corrupt_files_are_rejected_not_crashed(tmp_path, mutation):
 REF_SO = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "oracle", "_ref", "libxdrfile_ref.so")
 
 
-@pytest.mark.parametrize("seed", range(6))
-def test_writer_produces_the_reference_writers_bytes(tmp_path, seed):
-    """TrrWriter (src/io/trr_io.rs:441-520): random frames written by the library and by the reference's vendored C write_trr
-    (oracle/_ref) are the same bytes; the library's reader gets them back unchanged"""
-    if not os.path.exists(REF_SO):
-        pytest.skip("oracle/_ref not built (reference tree absent)")
+def writer_case(seed):
+    """-> (frames [(x, v, f)], 3x3 box) of test_writer_produces_the_reference_writers_bytes"""
+    rng = np.random.default_rng(88 + seed)
+    n = int(rng.choice([1, 3, 10, 50, 777]))
+    frames = [(rng.normal(0, 5, (n, 3)).astype(np.float32), rng.normal(0, 1, (n, 3)).astype(np.float32), rng.normal(0, 300, (n, 3)).astype(np.float32)) for _ in range(4)]
+    boxm = np.array([[7.5, 0, 0], [0, 6.5, 0], [1.0, 2.0, 5.5]], np.float32)
+    return frames, boxm
+
+
+def write_trr_with_ref(path, frames, boxm):
+    """the reference's vendored C write_trr (oracle/_ref), steps 100 i, times 0.5 i, lambda 0.25"""
     import ctypes as C
     lib = C.CDLL(REF_SO)
     lib.xdrfile_open.restype = C.c_void_p; lib.xdrfile_open.argtypes = [C.c_char_p, C.c_char_p]
     lib.xdrfile_close.argtypes = [C.c_void_p]
     lib.write_trr.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    rng = np.random.default_rng(88 + seed)
-    n = int(rng.choice([1, 3, 10, 50, 777]))
-    frames = [(rng.normal(0, 5, (n, 3)).astype(np.float32), rng.normal(0, 1, (n, 3)).astype(np.float32), rng.normal(0, 300, (n, 3)).astype(np.float32)) for _ in range(4)]
-    boxm = np.array([[7.5, 0, 0], [0, 6.5, 0], [1.0, 2.0, 5.5]], np.float32)
-    box9 = np.array(rows_to_box9(boxm.reshape(-1).tolist()), np.float32)
-    refp, ours = tmp_path / "ref.trr", tmp_path / "ours.trr"
-    fh = lib.xdrfile_open(str(refp).encode(), b"w")
+    n = frames[0][0].shape[0]
+    fh = lib.xdrfile_open(str(path).encode(), b"w")
     for i, (x, v, f) in enumerate(frames):
         assert lib.write_trr(fh, n, i * 100, C.c_float(0.5 * i), C.c_float(0.25), boxm.ctypes.data, x.ctypes.data, v.ctypes.data, f.ctypes.data) == 0
     lib.xdrfile_close(fh)
+
+
+@pytest.mark.parametrize("seed", range(6))
+def test_writer_produces_the_reference_writers_bytes(tmp_path, seed):
+    """TrrWriter (src/io/trr_io.rs:441-520): random frames written by the library and by the reference's vendored C write_trr
+    (oracle/_ref; the sha256 of its files pinned in tests/golden/ref_writer_pins.json) are the same bytes; the library's reader
+    gets them back unchanged"""
+    frames, boxm = writer_case(seed)
+    n = frames[0][0].shape[0]
+    box9 = np.array(rows_to_box9(boxm.reshape(-1).tolist()), np.float32)
+    refp, ours = tmp_path / "ref.trr", tmp_path / "ours.trr"
     with G.TrrWriter(ours) as w:
         for i, (x, v, f) in enumerate(frames):
             w.write_frame(x, box9, step=i * 100, time=0.5 * i, lambda_=0.25, velocities=v, forces=f)
-    assert open(ours, "rb").read() == open(refp, "rb").read()
+    assert hashlib.sha256(open(ours, "rb").read()).hexdigest() == ref_pin("trr_writer", seed)
+    if os.path.exists(REF_SO):
+        write_trr_with_ref(refp, frames, boxm)
+        assert open(ours, "rb").read() == open(refp, "rb").read()
     t = G.TrrFile(ours)
     assert t.n_frames == 4 and t.n_atoms == n
     for i, (x, v, f) in enumerate(frames):

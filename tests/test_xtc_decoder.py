@@ -2,8 +2,10 @@
   (1) committed data files of the reference's test suite with their expected decodes (tests/golden/xtc_expected.json
       = sha256 of the float stream the reference's vendored xdrfile produces, plus steps/times/boxes; tric_small.npz /
       short_traj.npz hold decoded coordinates), and
-  (2) when oracle/_ref is built: files written by the reference's xdrfile writer from synthetic coordinates that hit
-      every branch of the format (<= 9 atoms raw, water-like runs, wide ranges -> fixed-width fields, > 64-bit packing).
+  (2) files written by the reference's xdrfile writer from synthetic coordinates that hit every branch of the format (<= 9
+      atoms raw, water-like runs, wide ranges -> fixed-width fields, > 64-bit packing): the sha256 of each such file and of the
+      reference's decode of it are pinned in tests/golden/ref_writer_pins.json (tests/golden/make_ref_writer_pins.py); the
+      library's own encoder writes the pinned file, and where oracle/_ref is built the reference's writer and reader run as well.
 CPU only (the decoder is host code)."""
 import ctypes as C
 import hashlib
@@ -17,6 +19,16 @@ import pytest
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLD = os.path.join(HERE, "golden")
 REF_SO = os.path.join(os.path.dirname(HERE), "oracle", "_ref", "libxdrfile_ref.so")
+REF_PINS = os.path.join(GOLD, "ref_writer_pins.json")
+
+
+def ref_pin(kind, key):
+    """what the reference's writer (and reader) made of a synthetic case: tests/golden/make_ref_writer_pins.py"""
+    return json.load(open(REF_PINS))[kind][str(key)]
+
+
+def sha256_bytes(b):
+    return hashlib.sha256(b).hexdigest()
 
 
 @pytest.fixture(scope="module")
@@ -121,8 +133,11 @@ def water_like(rng, n, span):
     return np.concatenate([x, extra]).astype(np.float32)
 
 
-@pytest.mark.parametrize("case", ["tiny9", "water", "gas", "wide_range", "wide_product", "high_precision", "mixed"])
-def test_against_reference_writer(G, tmp_path, case):
+DECODER_CASES = ["tiny9", "water", "gas", "wide_range", "wide_product", "high_precision", "mixed"]
+
+
+def decoder_case(case):
+    """-> (frames, 3x3 box, precision) of test_against_reference_writer"""
     import zlib
     rng = np.random.default_rng(zlib.crc32(case.encode()))
     box = np.array([[30, 0, 0], [0, 30, 0], [10, 10, 25]], np.float32)
@@ -142,17 +157,36 @@ def test_against_reference_writer(G, tmp_path, case):
         frames = [water_like(rng, 3000, 6.0) for _ in range(3)]
     else:
         frames = [np.concatenate([water_like(rng, 9000, 12.0), rng.uniform(0, 12, (1000, 3)).astype(np.float32), water_like(rng, 2001, 3.0)]) for _ in range(4)]
-    path = tmp_path / (case + ".xtc")
-    write_with_ref(path, frames, box, prec)
+    return frames, box, prec
+
+
+@pytest.mark.parametrize("case", DECODER_CASES)
+def test_against_reference_writer(G, tmp_path, case):
+    frames, box, prec = decoder_case(case)
     n = frames[0].shape[0]
-    want = read_with_ref(path, n)
+    pin = ref_pin("xtc_decoder", case)
+    path = tmp_path / (case + ".xtc")
+    # the file the reference's writer writes (pinned; the library's encoder writes the same bytes), decoded by the reference's reader
+    with G.XtcWriter(path) as w:
+        for i, x in enumerate(frames):
+            w.write_frame(x, box9_from_rowmajor(box.ravel()), step=i * 10, time=i * 0.5, precision=prec)
+    assert sha256_bytes(open(path, "rb").read()) == pin["file_sha256"], case
+    if os.path.exists(REF_SO):
+        write_with_ref(path, frames, box, prec)
+        assert sha256_bytes(open(path, "rb").read()) == pin["file_sha256"], case
+        want = read_with_ref(path, n)
+        assert sha256_bytes(want.tobytes()) == pin["decode_sha256"], case
     x = G.XtcFile(path)
     assert x.n_atoms == n and x.n_frames == len(frames)
+    got = []
     for i in range(x.n_frames):
         pos, b9, step, time, p = x.read_frame(i)
-        assert np.array_equal(pos, want[i]), (case, i, np.abs(pos - want[i]).max())
+        got.append(pos)
+        if os.path.exists(REF_SO):
+            assert np.array_equal(pos, want[i]), (case, i, np.abs(pos - want[i]).max())
         assert step == i * 10 and time == np.float32(i * 0.5) and (n <= 9 or p == np.float32(prec))
         assert np.array_equal(b9, np.array([30, 30, 25, 0, 0, 0, 0, 10, 10], np.float32))
+    assert sha256_bytes(np.stack(got).tobytes()) == pin["decode_sha256"], case
     x.close()
 
 

@@ -3,8 +3,10 @@ writer writes (XtcWriter over xdrfile's write_xtc, src/io/xtc_io/mod.rs:256-331)
 trajectories are compared as files.
   (1) known answers: the committed data files of the reference's test suite.  Decoding is exact (test_xtc_decoder.py), and
       re-quantising a decoded coordinate returns its integer, so encode(decode(file)) has to reproduce the file itself;
-  (2) when oracle/_ref is built: synthetic coordinates through the reference's writer and through ours, same bytes, over
-      every branch of the format (raw <= 9 atoms, water runs, wide ranges, > 64-bit packing, precision 1e5, negative coordinates).
+  (2) synthetic coordinates through the reference's writer and through ours, same bytes, over every branch of the format (raw
+      <= 9 atoms, water runs, wide ranges, > 64-bit packing, precision 1e5, negative coordinates): the sha256 of the reference's
+      files (and of its decodes) are pinned in tests/golden/ref_writer_pins.json (tests/golden/make_ref_writer_pins.py); where
+      oracle/_ref is built, the reference's writer and reader run beside the pins.
 CPU only (host code)."""
 import os
 import zlib
@@ -12,7 +14,7 @@ import zlib
 import numpy as np
 import pytest
 
-from test_xtc_decoder import GOLD, REF_SO, read_with_ref, water_like, write_with_ref
+from test_xtc_decoder import GOLD, REF_SO, read_with_ref, ref_pin, sha256_bytes, water_like, write_with_ref
 
 
 @pytest.fixture(scope="module")
@@ -40,10 +42,11 @@ def test_reencoding_the_reference_files_reproduces_them(G, tmp_path, name):
     assert open(out, "rb").read() == open(src, "rb").read()
 
 
-@pytest.mark.parametrize("case", ["tiny9", "water", "gas", "negative", "wide_range", "wide_product", "high_precision", "mixed", "no_box_nan"])
-def test_same_bytes_as_the_reference_writer(G, tmp_path, case):
-    if not os.path.exists(REF_SO):
-        pytest.skip("oracle/_ref not built (reference tree absent)")
+SAME_BYTES_CASES = ["tiny9", "water", "gas", "negative", "wide_range", "wide_product", "high_precision", "mixed", "no_box_nan"]
+
+
+def same_bytes_case(case):
+    """-> (frames, 3x3 box, precision) of test_same_bytes_as_the_reference_writer"""
     rng = np.random.default_rng(zlib.crc32(case.encode()) + 1)
     boxm = np.array([[30, 0, 0], [0, 30, 0], [10, 10, 25]], np.float32)
     prec = 1000.0
@@ -61,8 +64,13 @@ def test_same_bytes_as_the_reference_writer(G, tmp_path, case):
         boxm = np.zeros((3, 3), np.float32)
     else:
         frames = [np.concatenate([water_like(rng, 9000, 12.0), rng.uniform(0, 12, (1000, 3)).astype(np.float32), water_like(rng, 2001, 3.0)]) for _ in range(4)]
+    return frames, boxm, prec
+
+
+@pytest.mark.parametrize("case", SAME_BYTES_CASES)
+def test_same_bytes_as_the_reference_writer(G, tmp_path, case):
+    frames, boxm, prec = same_bytes_case(case)
     ref_path, our_path = tmp_path / "ref.xtc", tmp_path / "ours.xtc"
-    write_with_ref(ref_path, frames, boxm, prec)
     with G.XtcWriter(our_path) as w:
         for i, f in enumerate(frames):
             g = f.copy()
@@ -70,10 +78,12 @@ def test_same_bytes_as_the_reference_writer(G, tmp_path, case):
                 g[5, 0] = np.nan                      # an atom without position is written as the origin
                 frames[i][5] = 0.0
             w.write_frame(g, None if case == "no_box_nan" else rows_to_box9(boxm), step=i * 10, time=i * 0.5, precision=prec)
-    if case == "no_box_nan":
+    a = open(our_path, "rb").read()
+    assert sha256_bytes(a) == ref_pin("xtc_writer", case), (case, len(a))
+    if os.path.exists(REF_SO):
         write_with_ref(ref_path, frames, boxm, prec)
-    a, b = open(our_path, "rb").read(), open(ref_path, "rb").read()
-    assert len(a) == len(b) and a == b, (case, len(a), len(b), next((k for k in range(min(len(a), len(b))) if a[k] != b[k]), None))
+        b = open(ref_path, "rb").read()
+        assert len(a) == len(b) and a == b, (case, len(a), len(b), next((k for k in range(min(len(a), len(b))) if a[k] != b[k]), None))
 
 
 def test_errors(G, tmp_path):
@@ -111,14 +121,8 @@ def test_coordinates_the_format_cannot_hold_are_refused(G, tmp_path):
     x.close()
 
 
-@pytest.mark.parametrize("seed", range(48))
-def test_random_systems_encode_to_the_reference_writers_bytes(G, tmp_path, seed):
-    """randomised byte-for-byte comparison with the reference's writer (oracle/_ref = the reference's vendored xdrfile compiled
-    where it lies): atom counts around the format's thresholds, coincident and collinear atoms (zero minimum step), identical
-    frames, runs of every length, molecules of 2-9 atoms, coordinates on the quantisation half-steps, mixed magnitudes,
-    several precisions"""
-    if not os.path.exists(REF_SO):
-        pytest.skip("oracle/_ref not built (reference tree absent)")
+def random_case(seed):
+    """-> (frames, 3x3 box, precision) of test_random_systems_encode_to_the_reference_writers_bytes"""
     rng = np.random.default_rng(31000 + seed)
     n = int(rng.choice([10, 11, 12, 13, 27, 100, 333, 1000, 2501]))
     prec = float(rng.choice([1000.0, 100.0, 10.0, 10000.0, 500.0]))
@@ -136,17 +140,35 @@ def test_random_systems_encode_to_the_reference_writers_bytes(G, tmp_path, seed)
             x = frames[-1].astype(np.float64)                                 # an identical frame
         frames.append(x.astype(np.float32))
     boxm = np.array([[span, 0, 0], [0, span, 0], [0, 0, span]], np.float32)
+    return frames, boxm, prec
+
+
+@pytest.mark.parametrize("seed", range(48))
+def test_random_systems_encode_to_the_reference_writers_bytes(G, tmp_path, seed):
+    """randomised byte-for-byte comparison with the reference's writer (oracle/_ref = the reference's vendored xdrfile compiled
+    where it lies; its files and decodes pinned in tests/golden/ref_writer_pins.json): atom counts around the format's
+    thresholds, coincident and collinear atoms (zero minimum step), identical frames, runs of every length, molecules of 2-9
+    atoms, coordinates on the quantisation half-steps, mixed magnitudes, several precisions"""
+    frames, boxm, prec = random_case(seed)
+    n = frames[0].shape[0]
+    pin = ref_pin("xtc_random", seed)
     ref_path, our_path = tmp_path / "ref.xtc", tmp_path / "ours.xtc"
-    write_with_ref(ref_path, frames, boxm, prec)
     with G.XtcWriter(our_path) as w:
         for i, fr in enumerate(frames):
             w.write_frame(fr, rows_to_box9(boxm), step=i * 10, time=i * 0.5, precision=prec)
-    a, b = open(our_path, "rb").read(), open(ref_path, "rb").read()
-    assert len(a) == len(b) and a == b, (seed, n, prec, span, mol, len(a), len(b), next((k for k in range(min(len(a), len(b))) if a[k] != b[k]), None))
+    a = open(our_path, "rb").read()
+    assert sha256_bytes(a) == pin["file_sha256"], (seed, n, prec, len(a))
+    if os.path.exists(REF_SO):
+        write_with_ref(ref_path, frames, boxm, prec)
+        b = open(ref_path, "rb").read()
+        assert len(a) == len(b) and a == b, (seed, n, prec, len(a), len(b), next((k for k in range(min(len(a), len(b))) if a[k] != b[k]), None))
+        want = read_with_ref(ref_path, n)
+        assert sha256_bytes(want.tobytes()) == pin["decode_sha256"], seed
     x = G.XtcFile(our_path)                                                  # and our decoder reads it back like the reference's
-    want = read_with_ref(ref_path, n)
-    for i in range(3):
-        assert np.array_equal(x.read_frame(i)[0], want[i])
+    got = np.stack([x.read_frame(i)[0] for i in range(3)])
+    if os.path.exists(REF_SO):
+        assert np.array_equal(got, want)
+    assert sha256_bytes(got.tobytes()) == pin["decode_sha256"], seed
     x.close()
 
 
