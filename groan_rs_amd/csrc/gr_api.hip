@@ -1151,7 +1151,7 @@ static int pairdist_launch(gr_ctx *c, uint32_t s0, uint32_t nb, const GrSel &s1,
         // orthorhombic loops are bound by the stores, and the mirror image's 256-byte runs cost more than half the arithmetic saves
         bool skewed = true;
         for (uint32_t f = 0; f < nb; ++f) skewed = skewed && !c->boxes_host[s0 + f].ortho;
-        const GrPdRed none = { 0, 0, 0.0f, 0u, nullptr, 0 };
+        const GrPdRed none = { 0, 0, 0.0f, 0u, nullptr, nullptr, 0 };
         const bool self = !red && c->pd_sym && skewed && s1.n == s2.n && s1.contiguous == s2.contiguous && s1.start == s2.start && s1.idx == s2.idx && s1.n >= 4 * GR_PDS_T;
         if (self) {
             const uint32_t nbk = (s1.n + GR_PDS_T - 1) / GR_PDS_T;
@@ -1284,24 +1284,30 @@ int gr_group_all_distances_reduce_batch(gr_ctx *c, uint32_t first_slot, uint32_t
     if (!out || out_capacity_bytes < (size_t)n_frames * len * (wide ? 8 : 4)) return fail(c, GR_E_INVALID_ARG, "output buffer too small");
     const bool sharded = op != GR_PD_HIST && !per_row;                         // whole-matrix values arrive in GR_PDR_SHARDS slots per frame
     const size_t words = sharded ? GR_PDR_SHARDS : len;
+    // histogram bins and whole-matrix counts accumulate in 64-bit words on the device (either can pass 2^32); min / max keys and per-row
+    // counts (bounded by the other group's size) in 32-bit ones
+    const bool acc64 = op == GR_PD_HIST || (op == GR_PD_COUNT_BELOW && !per_row);
+    const size_t word_bytes = acc64 ? sizeof(unsigned long long) : sizeof(uint32_t);
     const GrSel s1 = make_sel(*a), s2 = make_sel(*b);
     int first_err = GR_OK; std::string first_msg; uint64_t first_idx = 0;
     std::vector<uint32_t> host;
+    std::vector<unsigned long long> host64;
     for (uint32_t b0 = 0; b0 < n_frames; b0 += GR_MAX_BATCH) {
         const uint32_t nb = std::min<uint32_t>(GR_MAX_BATCH, n_frames - b0), s0 = first_slot + b0;
-        st = pairdist_reserve(c, ((size_t)nb * words + 1) & ~(size_t)1); if (st) return st;
+        st = pairdist_reserve(c, ((size_t)nb * words * (word_bytes / sizeof(float)) + 1) & ~(size_t)1); if (st) return st;
         uint32_t *acc = reinterpret_cast<uint32_t *>(c->pd_out);
-        HIPCHK(c, hipMemsetAsync(acc, op == GR_PD_MIN ? 0xFF : 0x00, (size_t)nb * words * sizeof(uint32_t), c->stream));
+        HIPCHK(c, hipMemsetAsync(acc, op == GR_PD_MIN ? 0xFF : 0x00, (size_t)nb * words * word_bytes, c->stream));
         std::vector<int> pre; std::vector<std::string> msg;
         batch_prechecks(c, s0, nb, true, pre, msg);
         // per row of a group of some size: the groups change places and every lane keeps the values of its own four atoms (k_pairdist,
         // "transposed"); a handful of rows against many columns stays as it is (the lanes are the columns)
         const bool transposed = per_row && a->n >= 512;
-        const GrPdRed red = { op, per_row ? (transposed ? 2 : 1) : 0, op == GR_PD_HIST ? (float)nbins / param : param, nbins, acc, words };
+        const GrPdRed red = { op, per_row ? (transposed ? 2 : 1) : 0, op == GR_PD_HIST ? (float)nbins / param : param, nbins, acc64 ? nullptr : acc,
+                              acc64 ? reinterpret_cast<unsigned long long *>(c->pd_out) : nullptr, words };
         st = transposed ? pairdist_launch(c, s0, nb, s2, s1, dim, nullptr, 0, &red) : pairdist_launch(c, s0, nb, s1, s2, dim, nullptr, 0, &red); if (st) return st;
         if (transposed) for (uint32_t f = 0; f < nb; ++f) std::swap(c->bad_host[4 * f], c->bad_host[4 * f + 1]);      // (first bad atom among the rows / the columns)
-        host.resize((size_t)nb * words);
-        HIPCHK(c, hipMemcpyAsync(host.data(), acc, host.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        if (acc64) { host64.resize((size_t)nb * words); HIPCHK(c, hipMemcpyAsync(host64.data(), acc, host64.size() * word_bytes, hipMemcpyDeviceToHost, c->stream)); }
+        else { host.resize((size_t)nb * words); HIPCHK(c, hipMemcpyAsync(host.data(), acc, host.size() * word_bytes, hipMemcpyDeviceToHost, c->stream)); }
         HIPCHK(c, hipStreamSynchronize(c->stream));
         for (uint32_t f = 0; f < nb; ++f) {
             int s = pre[f];
@@ -1309,12 +1315,18 @@ int gr_group_all_distances_reduce_batch(gr_ctx *c, uint32_t first_slot, uint32_t
             else s = pairdist_status(c, f, s1);
             if (s != GR_OK && first_err == GR_OK) { first_err = s; first_msg = c->err; first_idx = c->err_index; }
             if (status_out) status_out[b0 + f] = s;
-            const uint32_t *h = host.data() + (size_t)f * words;
             if (wide) {
                 uint64_t *o = static_cast<uint64_t *>(out) + (size_t)(b0 + f) * len;
-                if (sharded) { uint64_t v = 0; for (size_t k = 0; k < words; ++k) v += h[k]; o[0] = v; }
-                else for (size_t k = 0; k < len; ++k) o[k] = h[k];
+                if (acc64) {
+                    const unsigned long long *h = host64.data() + (size_t)f * words;
+                    if (sharded) { uint64_t v = 0; for (size_t k = 0; k < words; ++k) v += h[k]; o[0] = v; }
+                    else for (size_t k = 0; k < len; ++k) o[k] = h[k];
+                } else {
+                    const uint32_t *h = host.data() + (size_t)f * words;      // (per-row counts)
+                    for (size_t k = 0; k < len; ++k) o[k] = h[k];
+                }
             } else {
+                const uint32_t *h = host.data() + (size_t)f * words;
                 float *o = static_cast<float *>(out) + (size_t)(b0 + f) * len;
                 if (sharded) { uint32_t v = h[0]; for (size_t k = 1; k < words; ++k) v = op == GR_PD_MIN ? std::min(v, h[k]) : std::max(v, h[k]); o[0] = gr_key_f32(v); }
                 else for (size_t k = 0; k < len; ++k) o[k] = gr_key_f32(h[k]);
@@ -1327,7 +1339,7 @@ int gr_group_all_distances_reduce_batch(gr_ctx *c, uint32_t first_slot, uint32_t
 int gr_group_all_distances_reduce(gr_ctx *c, uint32_t slot, const char *g1, const char *g2, int dim, int op, int per_row, float param, uint32_t nbins,
                                   void *out, size_t out_capacity_bytes) try {
     int st = slot_check(c, slot); if (st) return st;
-    st = box_check(c, slot); if (st) return st;
+    // (no box check here: the groups are looked up first, as in gr_group_all_distances; the batch's prechecks report the box of the frame)
     return gr_group_all_distances_reduce_batch(c, slot, 1, g1, g2, dim, op, per_row, param, nbins, out, out_capacity_bytes, nullptr);
 } catch (...) { return gr_abi_guard(); }
 
@@ -1757,10 +1769,11 @@ int gr_group_center_batch(gr_ctx *c, uint32_t first_slot, uint32_t n_frames, con
 // atoms_center of the WHOLE system about a large contiguous reference group as ONE pass over HBM: the resident pass in its MODE 1 (gr_resident.h).
 // `done[f]` = 1: frame f is finished (its state is in c->state_host[f]); 0: the caller runs the two passes on it (the launch was not taken, never
 // started, was aborted before the frame, or handed the frame back -- an atom without position or mass, sums that are not finite);
-// `torn[f]` = 1: an aborted launch left the frame half-moved (reported as GR_E_HIP, as the RMSD-fit form does).
+// `torn[f]` = 1: an aborted launch left the frame half-moved (reported as GR_E_HIP, as the RMSD-fit form does);
+// `ran`: the launch started, so state_dev holds what its finalizers wrote (GR_ST_FALLBACK / GR_ST_ABORTED for the frames handed back).
 static int center_resident(gr_ctx *c, uint32_t s0, uint32_t nb, const GrSel &all, const GrSel &csel, int dim_mask, int weighted,
-                           const std::vector<int> &pre, std::vector<uint8_t> &done, std::vector<uint8_t> &torn) {
-    done.assign(nb, 0); torn.assign(nb, 0);
+                           const std::vector<int> &pre, std::vector<uint8_t> &done, std::vector<uint8_t> &torn, bool &ran) {
+    done.assign(nb, 0); torn.assign(nb, 0); ran = false;
     if (!c->center_resident || !csel.contiguous || csel.masked || !all.contiguous || all.start != 0 || all.n != c->n) return GR_OK;
     // which groups: the launch costs the same whatever the group -- 4.25 us per 1e6-atom frame in an orthorhombic cell, 4.35-4.4 in others -- while
     // the two passes shrink with it: orthorhombic (the one-float4-per-lane translate) 4.0 / 4.18 / 4.37 for a hundredth / a tenth / a fifth of the
@@ -1826,6 +1839,7 @@ static int center_resident(gr_ctx *c, uint32_t s0, uint32_t nb, const GrSel &all
     }
     c->res_backoff = 0;
     c->cen_res_launches++;
+    ran = true;
 #ifdef GR_EXP_STEPTIME
     if (getenv("GR_STEPTIME")) {
         unsigned long long st[32];
@@ -1925,7 +1939,8 @@ static int translate_batch_api(gr_ctx *c, uint32_t first_slot, uint32_t n_frames
         // atoms_center of the whole system about a large group: one pass over HBM where the resident pass takes it (center_resident); the frames
         // it did not finish -- all of them when it was not taken -- go through the two passes below, one run of consecutive frames at a time
         std::vector<uint8_t> done(nb, 0), torn(nb, 0);
-        if (cg) { st = center_resident(c, s0, nb, make_sel(*g), make_sel(*cg), mask[dim], weighted, pre, done, torn); if (st) return st; }
+        bool ran = false;
+        if (cg) { st = center_resident(c, s0, nb, make_sel(*g), make_sel(*cg), mask[dim], weighted, pre, done, torn, ran); if (st) return st; }
         bool any_done = false;
         for (uint32_t f = 0; f < nb; ++f) any_done = any_done || done[f];
         if (any_done) {
@@ -1952,6 +1967,8 @@ static int translate_batch_api(gr_ctx *c, uint32_t first_slot, uint32_t n_frames
             }
             continue;
         }
+        // (a launch that handed every frame back left its internal statuses in state_dev: the two passes start from the prechecks again)
+        if (ran) { st = states_from_prechecks(c, nb, pre); if (st) return st; }
         if (cg) { st = center_stage(c, s0, nb, make_sel(*cg), 1, weighted, 1, 0); if (st) return st; }   // group_estimate_center / _com per frame
         st = translate_batch(c, s0, nb, g, v, cg ? 1 : 2, cg ? mask[dim] : 7, pre, msg, status_out ? status_out + b0 : nullptr, first_err, first_msg, first_idx);
         if (st) return st;
@@ -3068,6 +3085,7 @@ __global__ __launch_bounds__(256) void k_trr_unpack(const unsigned char *__restr
         }
     }
     if (v[0] == 0.0f && v[1] == 0.0f && v[2] == 0.0f) v[0] = v[1] = v[2] = __uint_as_float(0x7fc00000u);      // (no position: NaN in x -- and, inside the library, in y and z: gr_layout.h::k_tile)
+    if (v[0] != v[0]) v[1] = v[2] = __uint_as_float(0x7fc00000u);     // (a NaN x in the file is no position as well: y and z follow it, as k_tile does)
     gr_pos_store(frames + (size_t)slots[k] * frame_stride, i, v[0], v[1], v[2]);
 }
 

@@ -1402,7 +1402,10 @@ enum { GR_PDR_MIN = 1, GR_PDR_MAX = 2, GR_PDR_COUNT_BELOW = 3, GR_PDR_HIST = 4 }
 #define GR_PDR_MAX_BINS 4096
 #define GR_PDR_ROW_TILES 8u        /* row tiles (of GR_PD_TI rows) a reducing workgroup walks */
 #define GR_PDR_SHARDS 256u         /* slots a frame's whole-matrix results are spread over (a power of two) */
-struct GrPdRed { int op, per_row; float param /* cut-off | bins per nm */; uint32_t nbins; uint32_t *out; size_t out_stride; };
+// out: 32-bit words -- min / max keys, and per-row counts (a row's count is bounded by the other group's size, < 2^32); wide: 64-bit words --
+// histogram bins and the whole-matrix count's shards, which may receive more than 2^32 entries (a bin of a 65 537-atom selection with itself,
+// a shard of a ~1.05e6-atom one); only one of the two is set, out_stride counts words of that one
+struct GrPdRed { int op, per_row; float param /* cut-off | bins per nm */; uint32_t nbins; uint32_t *out; unsigned long long *wide; size_t out_stride; };
 __host__ __device__ __forceinline__ uint32_t gr_f32_key(float f) { uint32_t b; memcpy(&b, &f, 4); return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u); }
 __host__ __device__ __forceinline__ float gr_key_f32(uint32_t k) { const uint32_t b = k ^ ((k >> 31) ? 0x80000000u : 0xFFFFFFFFu); float f; memcpy(&f, &b, 4); return f; }
 
@@ -1425,7 +1428,7 @@ __global__ __launch_bounds__(GR_WG) void k_pairdist(
     uint32_t red_col[4] = { red_key, red_key, red_key, red_key };
     const bool red_t = RED && red.per_row == 2, red_neg = red_t && dim >= 1 && dim <= 3;
     if (RED) {
-        red.out += (size_t)blockIdx.z * red.out_stride;
+        if (red.wide) red.wide += (size_t)blockIdx.z * red.out_stride; else red.out += (size_t)blockIdx.z * red.out_stride;
         if (threadIdx.x < GR_PD_TI) red_row[threadIdx.x] = red.op == GR_PDR_MIN ? 0xFFFFFFFFu : 0u;
         if (red.op == GR_PDR_HIST) for (uint32_t b = threadIdx.x; b < red.nbins; b += GR_WG) red_hist[b] = 0u;
     }
@@ -1597,7 +1600,7 @@ __global__ __launch_bounds__(GR_WG) void k_pairdist(
     if (RED) {
         __syncthreads();
         if (red.op == GR_PDR_HIST) {
-            for (uint32_t b = threadIdx.x; b < red.nbins; b += GR_WG) if (red_hist[b]) atomicAdd(red.out + b, red_hist[b]);
+            for (uint32_t b = threadIdx.x; b < red.nbins; b += GR_WG) if (red_hist[b]) atomicAdd(red.wide + b, (unsigned long long)red_hist[b]);   // (LDS bins: one workgroup's pairs, < 2^32)
         } else if (red_t) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
@@ -1615,8 +1618,9 @@ __global__ __launch_bounds__(GR_WG) void k_pairdist(
             if (threadIdx.x == 0) {
                 v = red_blk[0];
                 for (int w = 1; w < GR_WG / 64; ++w) v = comb(v, red_blk[w]);
-                uint32_t *o = red.out + ((blockIdx.y * gridDim.x + blockIdx.x) & (GR_PDR_SHARDS - 1u));     // one of the frame's slots: the host combines them
-                if (red.op == GR_PDR_MIN) atomicMin(o, v); else if (red.op == GR_PDR_MAX) atomicMax(o, v); else atomicAdd(o, v);
+                const uint32_t shard = (blockIdx.y * gridDim.x + blockIdx.x) & (GR_PDR_SHARDS - 1u);     // one of the frame's slots: the host combines them
+                if (red.op == GR_PDR_COUNT_BELOW) atomicAdd(red.wide + shard, (unsigned long long)v);
+                else if (red.op == GR_PDR_MIN) atomicMin(red.out + shard, v); else atomicMax(red.out + shard, v);
             }
         }
     }

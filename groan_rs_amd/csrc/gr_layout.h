@@ -20,6 +20,7 @@ __device__ __forceinline__ void gr_pos_load(const float *__restrict__ xyz, size_
     const size_t b = gr_tile_index(i, 0);            // y: + 2 floats inside the row or + 250 into the next, z likewise: one index computation
     x = xyz[b]; y = xyz[gr_tile_index(i, 1)]; z = xyz[gr_tile_index(i, 2)];
 }
+// invariant of every slot writer: an atom without position is NaN in x AND in y and z (k_translate_wrap_rows relies on it; not enforced here)
 __device__ __forceinline__ void gr_pos_store(float *__restrict__ xyz, size_t i, float x, float y, float z) {
     xyz[gr_tile_index(i, 0)] = x; xyz[gr_tile_index(i, 1)] = y; xyz[gr_tile_index(i, 2)] = z;
 }

@@ -646,7 +646,8 @@ class System:
     def group_all_distances_reduce(self, group1, group2, op, dim=Dimension.XYZ, per_row=False, param=0.0, nbins=0, first_slot=0, n_frames=1, raise_on_error=True):
         """what the callers of group_all_distances do with its matrix (analysis.rs:401-427; :1420-1451), without the matrix: `op` = "min" | "max"
         (float32), "count_below" (entries < param, uint64), "hist" (nbins bins over [0, param), uint64); per_row: one value per atom of
-        group1 instead of one per frame.  -> (array [n_frames, len], status[n_frames]); equal to the reduction of the full matrices"""
+        group1 instead of one per frame.  -> (array [n_frames, len], status[n_frames]); equal to the reduction of the full matrices.
+        Histogram bins, exactly: bin = (uint32_t)(d * s), s = (float)nbins / param in f32; counted iff d >= 0 and d * s < nbins"""
         opc = {"min": self.PD_MIN, "max": self.PD_MAX, "count_below": self.PD_COUNT_BELOW, "hist": self.PD_HIST}[op]
         length = nbins if opc == self.PD_HIST else (self.group_get_n_atoms(group1) if per_row else 1)
         out = np.zeros((n_frames, max(length, 1)), np.float32 if opc in (self.PD_MIN, self.PD_MAX) else np.uint64)

@@ -185,8 +185,9 @@ int gr_group_all_distances_batch_device(gr_ctx *ctx, uint32_t first_slot, uint32
  *   GR_PD_MIN / GR_PD_MAX     out = float[n_frames][per_row ? n1 : 1]: the smallest / largest entry of every row, or of the matrix
  *                             (1-D dimensions are signed, as in the matrix)
  *   GR_PD_COUNT_BELOW         out = uint64_t[n_frames][per_row ? n1 : 1]: entries < param
- *   GR_PD_HIST                out = uint64_t[n_frames][nbins]: entries d with 0 <= d, bin (uint32_t)(d * (float)nbins / param) < nbins, i.e.
- *                             nbins (<= 4096) bins over [0, param); per_row must be 0
+ *   GR_PD_HIST                out = uint64_t[n_frames][nbins]: nbins (<= 4096) bins over [0, param); per_row must be 0.  Exactly:
+ *                             bin = (uint32_t)(d * s), s = (float)nbins / param in f32; counted iff d >= 0 and d * s < nbins
+ *                             (one f32 product per entry: near bin edges this differs from (d * nbins) / param)
  * Errors and statuses as gr_group_all_distances_batch_device; the results equal the same reduction of that call's matrix exactly. */
 enum { GR_PD_MIN = 1, GR_PD_MAX = 2, GR_PD_COUNT_BELOW = 3, GR_PD_HIST = 4 };
 int gr_group_all_distances_reduce(gr_ctx *ctx, uint32_t slot, const char *group1, const char *group2, int dim, int op, int per_row, float param,

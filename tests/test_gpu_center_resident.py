@@ -135,3 +135,102 @@ def test_the_switch_takes_zero_or_one(G):
     with pytest.raises(G.DeviceError):
         s.set_tuning(center_resident=2)
     s.close()
+
+
+def run_counted(G, s, frames, box, group, nf, dim, weighted, mode, **tuning):
+    """one atoms_center_batch over fresh copies of the frames -> (positions, statuses, error index of the call, resident launches, frames
+    the launch handed back)"""
+    for f in range(nf):
+        s.set_frame(frames[f], box, slot=f)
+    s.set_tuning(center_resident=mode, **tuning)
+    launches, redone = s.stat("center_res_launches"), s.stat("center_res_redone")
+    st = np.array(s.atoms_center_batch(group, 0, nf, dim, weighted=weighted, raise_on_error=False))
+    idx = int(s._lib.gr_last_error_index(s._ctx))
+    return ([s.get_positions(f) for f in range(nf)], st, idx, s.stat("center_res_launches") - launches, s.stat("center_res_redone") - redone)
+
+
+def test_every_frame_handed_back_for_a_massless_atom(G):
+    """a weighted centre whose (contiguous) reference group holds an atom without mass: the launch hands back EVERY frame and no frame failed
+    a host check -- the two passes must then report the reference's MassError with the atom's index, not the launch's internal status"""
+    box = O.box_from_lengths_angles([9.0, 8.5, 8.0], [90.0, 90.0, 90.0])
+    n, nf, bad = 60_000, 12, 12_345
+    s, frames, m = build(G, n, nf, box, 17)
+    m = m.copy(); m[bad] = np.nan
+    s.set_masses(m)
+    s.group_create_from_ranges("half", [(0, n // 2)])
+    res = {mode: run_counted(G, s, frames, box, "half", nf, G.Dimension.XYZ, True, mode, resident=2) for mode in (1, 0)}
+    assert res[1][3] == 1 and res[1][4] == nf, "the resident launch did not run, or did not hand every frame back"
+    assert res[0][3] == 0
+    assert (res[1][1] == G._lib.E_NO_MASS).all(), res[1][1]
+    assert np.array_equal(res[1][1], res[0][1]) and res[1][2] == res[0][2] == bad
+    for f in range(nf):
+        assert np.array_equal(res[1][0][f], frames[f]) and np.array_equal(res[0][0][f], frames[f]), f      # failed frames are untouched
+    # the raising call names the atom, whichever path takes it
+    for mode in (1, 0):
+        for f in range(nf):
+            s.set_frame(frames[f], box, slot=f)
+        s.set_tuning(center_resident=mode, resident=2)
+        launches = s.stat("center_res_launches")
+        with pytest.raises(G.GroupError) as e:
+            s.atoms_center_batch("half", 0, nf, G.Dimension.XYZ, weighted=True)
+        assert e.value.variant == "InvalidMass" and e.value.detail == bad and s.stat("center_res_launches") == launches + mode
+    # the same masses, unweighted: masses are not read, the launch moves every frame itself
+    res = {mode: run_counted(G, s, frames, box, "half", nf, G.Dimension.XYZ, False, mode, resident=2) for mode in (1, 0)}
+    assert res[1][3] == 1 and res[1][4] == 0
+    assert (res[1][1] == 0).all() and (res[0][1] == 0).all(), (res[1][1], res[0][1])
+    for f in range(nf):
+        assert np.array_equal(res[1][0][f], res[0][0][f]), (f, np.abs(res[1][0][f] - res[0][0][f]).max())
+        assert not np.array_equal(res[1][0][f], frames[f])
+    s.close()
+
+
+def test_every_frame_handed_back_for_atoms_without_position(G):
+    """every frame holds one atom without position -- inside the reference group in some frames, outside it in others: every frame is handed
+    back, and each must report GR_E_NO_POSITION with its own atom's index, as the two passes do"""
+    box = O.box_from_lengths_angles([9.0, 8.5, 8.0], [90.0, 90.0, 90.0])
+    n, nf = 60_000, 10
+    s, frames, m = build(G, n, nf, box, 23)
+    s.group_create_from_ranges("half", [(0, n // 2)])
+    rng = np.random.default_rng(23)
+    nan_at = [int(rng.integers(0, n // 2)) if f % 2 == 0 else int(rng.integers(n // 2 + 1, n)) for f in range(nf)]   # inside / outside
+    for f in range(nf):
+        frames[f] = frames[f].copy(); frames[f][nan_at[f]] = np.nan
+    res = {mode: run_counted(G, s, frames, box, "half", nf, G.Dimension.XYZ, True, mode, resident=2) for mode in (1, 0)}
+    assert res[1][3] == 1 and res[1][4] == nf, "the resident launch did not run, or did not hand every frame back"
+    assert (res[1][1] == G._lib.E_NO_POSITION).all(), res[1][1]
+    assert np.array_equal(res[1][1], res[0][1]) and res[1][2] == res[0][2] == nan_at[0]
+    for f in range(nf):
+        assert np.array_equal(res[1][0][f], res[0][0][f], equal_nan=True), f
+    # each frame's own index: one frame per call, the launch forced on every one
+    for f in range(nf):
+        for mode in (1, 0):
+            s.set_frame(frames[f], box, slot=f)
+            s.set_tuning(center_resident=mode, resident=2)
+            launches = s.stat("center_res_launches")
+            with pytest.raises(G.GroupError) as e:
+                s.atoms_center_batch("half", f, 1, G.Dimension.XYZ, weighted=True)
+            assert e.value.variant == "InvalidPosition" and e.value.detail == nan_at[f], (f, mode, e.value.detail)
+            assert s.stat("center_res_launches") == launches + mode
+    s.close()
+
+
+def test_a_launch_aborted_before_any_frame_finished(G):
+    """frame 0's finalizer aborts the launch and no frame failed a host check -- in a batch of 20 frames and in a batch of that one frame,
+    where nothing can have finished: the frames not finished go through the two passes, and no internal status (GR_ST_FALLBACK 100,
+    GR_ST_ABORTED 102) reaches the caller"""
+    box = O.box_from_lengths_angles([9.0, 8.5, 8.0], [60.0, 60.0, 90.0])
+    n, nf = 60_000, 20
+    s, frames, m = build(G, n, nf, box, 29)
+    for nb in (nf, 1):
+        want = run_counted(G, s, frames, box, "all", nb, G.Dimension.XYZ, True, 0)
+        assert (want[1] == 0).all() and want[3] == 0
+        aborts = s.stat("res_aborts")
+        got = run_counted(G, s, frames, box, "all", nb, G.Dimension.XYZ, True, 1, resident=2, resident_streams=1, test_resident_abort_at=0)
+        assert got[3] == 1 and s.stat("res_aborts") == aborts + 1, "the resident launch did not run, or was not aborted"
+        assert not np.isin(got[1], [100, 102]).any(), (nb, got[1])
+        assert np.isin(got[1], [0, G._lib.E_HIP]).all(), (nb, got[1])           # (a frame caught half-moved is reported, never silent)
+        for f in range(nb):
+            if got[1][f] == 0:
+                assert np.array_equal(got[0][f], want[0][f]), (nb, f)
+        assert (got[1] == 0).sum() >= nb - 8
+    s.close()
