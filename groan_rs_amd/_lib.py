@@ -17,7 +17,7 @@ c_i32p = C.POINTER(C.c_int)
 # status codes (include/groan_hip.h)
 (OK, E_NO_BOX, E_NOT_ORTHOGONAL, E_ZERO_BOX, E_EMPTY_GROUP, E_INCONSISTENT_GROUP, E_NO_POSITION, E_NO_MASS,
  E_GROUP_NOT_FOUND, E_OUT_OF_RANGE, E_INVALID_ARG, E_GROUP_EXISTS, E_HIP, E_NO_DEVICE, E_UNSUPPORTED_BOX, E_IO, E_FORMAT,
- E_INVALID_NAME) = range(18)
+ E_INVALID_NAME, E_EMPTY_CHAIN, E_NONEXISTENT_CHAIN, E_DUPLICATE_PAIR, E_UNUSED_CHAIN) = range(22)
 
 CENTER_NAIVE, CENTER_ESTIMATE, CENTER_PBC = 0, 1, 2
 
@@ -119,6 +119,10 @@ SIGNATURES = {
     "gr_ndx_group_indices": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
     "gr_ndx_install": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "gr_group_pairs_within": (C.c_int, [C.c_void_p, C.c_uint32, C.c_char_p, C.c_char_p, C.c_float, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "gr_hbond_plan_create": (C.c_void_p, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_float, C.c_float, c_i32p]),
+    "gr_hbond_plan_destroy": (None, [C.c_void_p]),
+    "gr_hbond_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 c_u64p, C.c_void_p]),
     "gr_group_center_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "gr_group_translate_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_void_p, C.c_void_p]),
     "gr_group_wrap_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_void_p]),

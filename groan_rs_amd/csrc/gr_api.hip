@@ -743,6 +743,10 @@ const char *gr_status_string(int s) try {
     case GR_E_IO: return "file could not be opened or read";
     case GR_E_FORMAT: return "not a valid xtc file";
     case GR_E_INVALID_NAME: return "invalid group name";
+    case GR_E_EMPTY_CHAIN: return "no acceptor and no donor atoms detected for chain";
+    case GR_E_NONEXISTENT_CHAIN: return "chain does not exist";
+    case GR_E_DUPLICATE_PAIR: return "pair of chains requested multiple times";
+    case GR_E_UNUSED_CHAIN: return "not all chains are used";
     default: return "unknown status";
     }
 } catch (...) { return nullptr; }
@@ -3738,3 +3742,5 @@ int gr_synth_uniform(gr_ctx *c, uint32_t slot, const float *box9, uint64_t seed)
 } catch (...) { return gr_abi_guard(); }
 
 }  // extern "C"
+
+#include "gr_hbonds.h"   // hydrogen bonds: kernels, plan and C ABI (after the context and its helpers)

@@ -69,6 +69,11 @@ class TrajReader:
     def calc_rmsd_and_fit(self, reference, group):
         return TrajConverterAnalyzer(self, RMSDConverterAnalyzer(reference, self.system, group))
 
+    # HBondTrajRead (hbonds.rs:404-485): the plan is built (and its errors raised) here, each frame yields its HBondMap
+    def hbonds_analyze(self, chains, pairs, max_distance, min_angle, bonds):
+        from .hbonds import HBondAnalysis
+        return TrajAnalyzer(self, HBondAnalysis(self.system, chains, pairs, max_distance, min_angle, bonds, slot=self.slot))
+
 
 class TrajConverter:                     # traj_convert.rs:14-57
     def __init__(self, reader, converter):

@@ -38,6 +38,7 @@ extern "C" {
 
 typedef struct gr_ctx gr_ctx;
 typedef struct gr_rmsd_plan gr_rmsd_plan;
+typedef struct gr_hbond_plan gr_hbond_plan;
 typedef struct gr_xtc gr_xtc;
 
 /* status codes; 1..7 map onto the reference's error enums (src/errors.rs) */
@@ -61,7 +62,11 @@ enum {
                                     dodecahedral and octahedral cells need 4-8.  Refused rather than answered approximately. */
     GR_E_IO = 15,                /* ReadTrajError::FileNotFound / read failure              */
     GR_E_FORMAT = 16,            /* ReadTrajError::NotXtc / FrameNotFound (corrupt stream)  */
-    GR_E_INVALID_NAME = 17       /* GroupError::InvalidName (auxiliary.rs:37-51)            */
+    GR_E_INVALID_NAME = 17,      /* GroupError::InvalidName (auxiliary.rs:37-51)            */
+    GR_E_EMPTY_CHAIN = 18,       /* HBondError::EmptyChain (errors.rs:675-677); index = chain   */
+    GR_E_NONEXISTENT_CHAIN = 19, /* HBondError::NonexistentChain(chain); index = chain          */
+    GR_E_DUPLICATE_PAIR = 20,    /* HBondError::PairSpecifiedMultipleTimes; index = ordinal of the repeated pair */
+    GR_E_UNUSED_CHAIN = 21       /* HBondError::UnusedChain                                      */
 };
 
 /* Dimension (src/structures/dimension.rs:13-23) */
@@ -401,6 +406,34 @@ int gr_ndx_install(const gr_ndx *x, gr_ctx *ctx, size_t *n_invalid_names, size_t
  * written -- when *n_pairs > max_pairs call again with larger buffers (the buffers may be NULL to just count). */
 int gr_group_pairs_within(gr_ctx *ctx, uint32_t slot, const char *group1, const char *group2, float cutoff, uint64_t max_pairs,
                           uint32_t *i_out, uint32_t *j_out, float *dist_out, uint64_t *n_pairs);
+
+/* ---------------------------------------------------------------- hydrogen bonds over a batch of resident frames
+ * HBondAnalysis / HBondTrajRead::hbonds_analyze (src/system/hbonds.rs:154-373).  A plan is built once: `groups` holds
+ * n_chains x 3 group names of the context (acceptors, donors, hydrogens of each chain), `pairs` n_pairs x 2 chain indices,
+ * `bonds` n_bonds x 2 atom indices (either order; the context has no topology: the caller passes its system's bonds).  A donor
+ * is kept when it is bonded to an atom of its chain's hydrogen group; its hydrogens are taken in index order.  Plan errors, in
+ * the reference's order: GR_E_OUT_OF_RANGE (a bonded atom outside the system, index = the atom), per chain GR_E_GROUP_NOT_FOUND
+ * and GR_E_EMPTY_CHAIN (index = the chain), then the pairs: GR_E_NONEXISTENT_CHAIN (index = the chain), GR_E_DUPLICATE_PAIR
+ * ((0,1) after (1,0) counts; index = the ordinal of the repeated pair), GR_E_UNUSED_CHAIN; then max_distance <= 0
+ * (GR_E_INVALID_ARG: the reference's CellGridError::InvalidCellSize).  The plan keeps a pointer to the context: destroy it first.
+ *
+ * gr_hbond_batch analyses the n_frames (<= 1024) slots from first_slot.  The bonds of frame f and pair p are the entries
+ * offsets[f * n_pairs + p] .. offsets[f * n_pairs + p + 1] (offsets holds n_frames * n_pairs + 1 values and is always written),
+ * ordered as the reference's segments ((a, a): donors of a to acceptors of a; (a, b): donors of b to acceptors of a, then donors
+ * of a to acceptors of b), then by donor (group order), acceptor index and hydrogen index.  distance = acceptor.distance(donor)
+ * in nm; angle = the donor-hydrogen...acceptor angle in degrees (a NaN angle is 180 when the hydrogen is closer to the acceptor
+ * than the donor, else 0).  *n_total receives the batch's number of bonds; when it exceeds max_bonds, or any output pointer is
+ * NULL, no bond is written (count only).  Every frame is judged on its own: status_out[f] (may be NULL) receives GR_OK,
+ * GR_E_NO_BOX / GR_E_ZERO_BOX / GR_E_NOT_ORTHOGONAL (strict mode) / GR_E_UNSUPPORTED_BOX, or GR_E_NO_POSITION -- the first
+ * acceptor (chains in order, then group order), else the first donor without position, else, for the first donor with an
+ * acceptor within max_distance, its first hydrogen without position; a failed frame has empty segments.  The return value is
+ * the first failed frame's status (message and gr_last_error_index as for the single calls).  Non-orthogonal boxes are
+ * supported outside strict mode, as in gr_group_pairs_within. */
+gr_hbond_plan *gr_hbond_plan_create(gr_ctx *ctx, const char *const *groups, uint32_t n_chains, const uint32_t *pairs, uint32_t n_pairs,
+                                    const uint64_t *bonds, uint64_t n_bonds, float max_distance, float min_angle, int *status);
+void gr_hbond_plan_destroy(gr_hbond_plan *plan);
+int gr_hbond_batch(gr_hbond_plan *plan, uint32_t first_slot, uint32_t n_frames, uint64_t max_bonds, uint32_t *donor, uint32_t *hydrogen,
+                   uint32_t *acceptor, float *distance, float *angle, uint64_t *offsets, uint64_t *n_total, int *status_out);
 
 /* ---------------------------------------------------------------- per-frame analyses over a batch of slots
  * The calls above for `n_frames` consecutive slots in ONE set of launches and one read-back (a trajectory loop of

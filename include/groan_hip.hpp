@@ -536,4 +536,76 @@ Data traj_iter_map_reduce(const std::vector<int> &devices, uint64_t n_frames,
     return Data::reduce(std::move(data));
 }
 
+// ---- hydrogen bonds over a batch of resident frames (src/system/hbonds.rs): HBondAnalysis as a plan built once
+struct HBondChain { std::string acceptors, donors, hydrogens; };   // group names of the System (HBondChain::new)
+struct HBond { uint32_t donor, hydrogen, acceptor; float distance, angle; };
+
+class HBondPlan {
+  public:
+    // bonds: the System's bonds as atom pairs (either order); errors carry the reference's HBondError variant names
+    HBondPlan(System &system, const std::vector<HBondChain> &chains, const std::vector<std::pair<uint32_t, uint32_t>> &pairs,
+              const std::vector<std::pair<uint64_t, uint64_t>> &bonds, float max_distance, float min_angle)
+        : ctx_(system.raw()), pairs_(pairs) {
+        std::vector<const char *> names;
+        for (const auto &c : chains) { names.push_back(c.acceptors.c_str()); names.push_back(c.donors.c_str()); names.push_back(c.hydrogens.c_str()); }
+        std::vector<uint32_t> pr; for (const auto &p : pairs) { pr.push_back(p.first); pr.push_back(p.second); }
+        std::vector<uint64_t> bd; for (const auto &b : bonds) { bd.push_back(b.first); bd.push_back(b.second); }
+        int st = 0;
+        plan_ = gr_hbond_plan_create(ctx_, names.data(), (uint32_t)chains.size(), pr.data(), (uint32_t)pairs.size(), bd.data(), bonds.size(), max_distance, min_angle, &st);
+        if (!plan_) raise(st, true);
+    }
+    ~HBondPlan() { if (plan_) gr_hbond_plan_destroy(plan_); }
+    HBondPlan(const HBondPlan &) = delete;
+    HBondPlan &operator=(const HBondPlan &) = delete;
+    HBondPlan(HBondPlan &&o) noexcept : ctx_(o.ctx_), plan_(o.plan_), pairs_(std::move(o.pairs_)), cap_(o.cap_) { o.plan_ = nullptr; }
+
+    // the bonds of n_frames resident slots: result[f][p] = bonds of frame f and pair p (HBondMap in pair order); a frame that
+    // failed throws the first failure unless `status` is given, which then receives every frame's status
+    std::vector<std::vector<std::vector<HBond>>> batch(uint32_t first_slot, uint32_t n_frames, std::vector<int> *status = nullptr) {
+        const size_t np = pairs_.size();
+        std::vector<uint64_t> offs((size_t)n_frames * np + 1);
+        std::vector<int> st(n_frames);
+        uint64_t total = 0;
+        std::vector<uint32_t> d, h, a; std::vector<float> dist, ang;
+        int r = GR_OK;
+        for (int pass = 0; pass < 2; ++pass) {
+            d.resize(cap_ + 1); h.resize(cap_ + 1); a.resize(cap_ + 1); dist.resize(cap_ + 1); ang.resize(cap_ + 1);
+            r = gr_hbond_batch(plan_, first_slot, n_frames, cap_, d.data(), h.data(), a.data(), dist.data(), ang.data(), offs.data(), &total, st.data());
+            if (total <= cap_) break;
+            cap_ = total + total / 4;                                    // capacity hint: one call per batch in steady state
+        }
+        if (status) *status = st;
+        else if (r != GR_OK) raise(r, false);
+        std::vector<std::vector<std::vector<HBond>>> out(n_frames, std::vector<std::vector<HBond>>(np));
+        for (uint32_t f = 0; f < n_frames; ++f)
+            for (size_t p = 0; p < np; ++p)
+                for (uint64_t k = offs[f * np + p]; k < offs[f * np + p + 1]; ++k) out[f][p].push_back(HBond{ d[k], h[k], a[k], dist[k], ang[k] });
+        return out;
+    }
+    const std::vector<std::pair<uint32_t, uint32_t>> &pairs() const { return pairs_; }
+    gr_hbond_plan *raw() const { return plan_; }
+
+  private:
+    [[noreturn]] void raise(int st, bool plan) const {
+        const uint64_t idx = gr_last_error_index(ctx_);
+        switch (st) {
+        case GR_E_EMPTY_CHAIN: throw Error("HBondError", "EmptyChain", st, idx);
+        case GR_E_NONEXISTENT_CHAIN: throw Error("HBondError", "NonexistentChain", st, idx);
+        case GR_E_DUPLICATE_PAIR: throw Error("HBondError", "PairSpecifiedMultipleTimes", st, idx);   // index = the repeated pair's ordinal
+        case GR_E_UNUSED_CHAIN: throw Error("HBondError", "UnusedChain", st);
+        case GR_E_GROUP_NOT_FOUND: throw Error("HBondError", "SelectError", st);
+        case GR_E_NO_POSITION: throw Error("HBondError", "AtomError(InvalidPosition)", st, idx);
+        case GR_E_OUT_OF_RANGE: throw Error("HBondError", "AtomError(OutOfRange)", st, idx);
+        case GR_E_NO_BOX: case GR_E_NOT_ORTHOGONAL: case GR_E_ZERO_BOX: throw Error("HBondError", "InvalidSimBox(" + simbox_variant(st) + ")", st);
+        default:
+            if (plan && st == GR_E_INVALID_ARG) throw Error("HBondError", "CellGridError(InvalidCellSize)", st);
+            throw Error("DeviceError", std::string(gr_status_string(st)) + ": " + gr_last_error(ctx_), st);
+        }
+    }
+    gr_ctx *ctx_ = nullptr;
+    gr_hbond_plan *plan_ = nullptr;
+    std::vector<std::pair<uint32_t, uint32_t>> pairs_;
+    uint64_t cap_ = 0;
+};
+
 }  // namespace groan

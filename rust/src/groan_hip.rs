@@ -9,8 +9,8 @@
 use std::ffi::{c_char, c_float, c_int, c_void, CString};
 use std::marker::PhantomData;
 
-use crate::errors::{AtomError, GroupError, MassError, PositionError, RMSDError, SimBoxError};
-use crate::structures::{container::AtomContainer, dimension::Dimension, simbox::SimBox, vector3d::Vector3D};
+use crate::errors::{AtomError, CellGridError, GroupError, HBondError, MassError, PositionError, RMSDError, SimBoxError};
+use crate::structures::{container::AtomContainer, dimension::Dimension, group::Group, simbox::SimBox, vector3d::Vector3D};
 use crate::system::System;
 use crate::structures::traj_convert::{FrameAnalyze, FrameConvertAnalyze};
 
@@ -26,7 +26,14 @@ pub const GR_E_INCONSISTENT_GROUP: c_int = 5;
 pub const GR_E_NO_POSITION: c_int = 6;
 pub const GR_E_NO_MASS: c_int = 7;
 pub const GR_E_GROUP_NOT_FOUND: c_int = 8;
+pub const GR_E_OUT_OF_RANGE: c_int = 9;
+pub const GR_E_INVALID_ARG: c_int = 10;
+pub const GR_E_EMPTY_CHAIN: c_int = 18;
+pub const GR_E_NONEXISTENT_CHAIN: c_int = 19;
+pub const GR_E_DUPLICATE_PAIR: c_int = 20;
+pub const GR_E_UNUSED_CHAIN: c_int = 21;
 
+#[repr(C)] pub struct gr_hbond_plan { _private: [u8; 0] }
 #[repr(C)] pub struct gr_pool { _private: [u8; 0] }
 #[repr(C)] pub struct gr_comm { _private: [u8; 0] }
 /// `body(ctx, worker, frame, user, result)` of gr_pool_map: non-zero return = the frame's error (the first one wins)
@@ -54,6 +61,12 @@ extern "C" {
                                          nbins: u32, out: *mut c_void, out_capacity_bytes: usize) -> c_int;
     pub fn gr_group_all_distances_reduce_batch(ctx: *mut gr_ctx, first_slot: u32, n_frames: u32, g1: *const c_char, g2: *const c_char, dim: c_int, op: c_int,
                                                per_row: c_int, param: c_float, nbins: u32, out: *mut c_void, out_capacity_bytes: usize, status_out: *mut c_int) -> c_int;
+    // hydrogen bonds over a batch of resident frames (hbonds.rs:154-373); groups = n_chains x (acceptors, donors, hydrogens)
+    pub fn gr_hbond_plan_create(ctx: *mut gr_ctx, groups: *const *const c_char, n_chains: u32, pairs: *const u32, n_pairs: u32, bonds: *const u64, n_bonds: u64,
+                                max_distance: c_float, min_angle: c_float, status: *mut c_int) -> *mut gr_hbond_plan;
+    pub fn gr_hbond_plan_destroy(plan: *mut gr_hbond_plan);
+    pub fn gr_hbond_batch(plan: *mut gr_hbond_plan, first_slot: u32, n_frames: u32, max_bonds: u64, donor: *mut u32, hydrogen: *mut u32, acceptor: *mut u32,
+                          distance: *mut c_float, angle: *mut c_float, offsets: *mut u64, n_total: *mut u64, status_out: *mut c_int) -> c_int;
     pub fn gr_trr_open(path: *const c_char, status: *mut c_int) -> *mut gr_trr;
     pub fn gr_trr_close(trr: *mut gr_trr);
     pub fn gr_trr_n_atoms(trr: *const gr_trr) -> u64;
@@ -391,6 +404,97 @@ impl FrameConvertAnalyze for HipRmsd {
                 Ok(r)
             }
             s => Err(rmsd_error(&self.target, s, &self.group)),
+        }
+    }
+}
+
+/// One hydrogen bond as `HBond` reports it (hbonds.rs:51-70, whose constructor is private to its module): the same getters.
+#[derive(Debug, Clone, Copy, PartialEq)]
+pub struct HipHBond { donor: usize, hydrogen: usize, acceptor: usize, distance: f32, angle: f32 }
+
+impl HipHBond {
+    pub fn donor(&self) -> usize { self.donor }
+    pub fn hydrogen(&self) -> usize { self.hydrogen }
+    pub fn acceptor(&self) -> usize { self.acceptor }
+    pub fn distance(&self) -> f32 { self.distance }
+    pub fn angle(&self) -> f32 { self.angle }
+}
+
+/// `HBondAnalysis` (src/system/hbonds.rs:154-373) on the GPU: chains are (acceptors, donors, hydrogens) GSL queries as in
+/// `HBondChain::new`, the bonds are the System's own.  `system.xtc_iter(f)?.analyze(HipHBonds::new(..)?)` yields, per frame,
+/// the bonds of every requested pair in the reference's order.
+pub struct HipHBonds { plan: *mut gr_hbond_plan, sys: HipSystem, pairs: Vec<(usize, usize)>, scratch: Vec<[f32; 3]>, cap: u64 }
+
+impl Drop for HipHBonds { fn drop(&mut self) { unsafe { gr_hbond_plan_destroy(self.plan) } } }
+
+impl HipHBonds {
+    pub fn new(system: &System, chains: &[(&str, &str, &str)], pairs: Vec<(usize, usize)>, max_distance: f32, min_angle: f32, device: i32)
+        -> Result<Self, HBondError> {
+        let sys = HipSystem::new(system, device, 1).ok_or(HBondError::EmptyChain)?;
+        let mut names = Vec::new();
+        for (k, (a, d, h)) in chains.iter().enumerate() {
+            for (r, q) in [a, d, h].iter().enumerate() {
+                let group = Group::from_query(q, system).map_err(HBondError::SelectError)?;
+                let name = format!("__hbond_{}_{}", k, r);
+                sys.group_from_container(&name, group.get_atoms());
+                names.push(CString::new(name).unwrap());
+            }
+        }
+        let ptrs: Vec<*const c_char> = names.iter().map(|n| n.as_ptr()).collect();
+        let flat: Vec<u32> = pairs.iter().flat_map(|&(a, b)| [a as u32, b as u32]).collect();
+        let mut bonds = Vec::new();
+        for i in 0..system.get_n_atoms() {
+            for j in system.bonded_atoms_iter(i).unwrap() {
+                if j.get_index() > i { bonds.push(i as u64); bonds.push(j.get_index() as u64); }
+            }
+        }
+        let mut st = 0;
+        let plan = unsafe { gr_hbond_plan_create(sys.ctx, ptrs.as_ptr(), chains.len() as u32, flat.as_ptr(), pairs.len() as u32, bonds.as_ptr(),
+                                                 (bonds.len() / 2) as u64, max_distance, min_angle, &mut st) };
+        if plan.is_null() { return Err(hbond_error(&sys, st, &pairs, true)); }
+        Ok(HipHBonds { plan, sys, pairs, scratch: Vec::new(), cap: 0 })
+    }
+}
+
+fn hbond_error(sys: &HipSystem, status: c_int, pairs: &[(usize, usize)], plan: bool) -> HBondError {
+    let idx = unsafe { gr_last_error_index(sys.ctx) } as usize;
+    match status {
+        GR_E_EMPTY_CHAIN => HBondError::EmptyChain,
+        GR_E_NONEXISTENT_CHAIN => HBondError::NonexistentChain(idx),
+        GR_E_DUPLICATE_PAIR => HBondError::PairSpecifiedMultipleTimes(pairs[idx].0, pairs[idx].1),
+        GR_E_UNUSED_CHAIN => HBondError::UnusedChain,
+        GR_E_INVALID_ARG if plan => HBondError::CellGridError(CellGridError::InvalidCellSize),
+        GR_E_NO_POSITION => HBondError::AtomError(AtomError::InvalidPosition(PositionError::NoPosition(idx))),
+        GR_E_OUT_OF_RANGE => HBondError::AtomError(AtomError::OutOfRange(idx)),
+        s => HBondError::InvalidSimBox(simbox_err(s)),
+    }
+}
+
+impl FrameAnalyze for HipHBonds {
+    type Error = HBondError;
+    /// per requested pair, in the order of `pairs`: ((chain1, chain2), bonds) -- the entries of the reference's HBondMap
+    type AnalysisResult = Vec<((usize, usize), Vec<HipHBond>)>;
+    fn analyze(&mut self, system: &System) -> Result<Self::AnalysisResult, HBondError> {
+        self.scratch.clear();
+        self.scratch.extend(system.atoms_iter().map(|a| a.get_position().map_or([f32::NAN; 3], |p| [p.x, p.y, p.z])));
+        self.sys.upload(0, &self.scratch, system.get_box());
+        let np = self.pairs.len();
+        let mut offs = vec![0u64; np + 1];
+        let (mut total, mut st) = (0u64, 0);
+        loop {
+            let n = self.cap as usize + 1;
+            let (mut d, mut h, mut a) = (vec![0u32; n], vec![0u32; n], vec![0u32; n]);
+            let (mut dist, mut ang) = (vec![0f32; n], vec![0f32; n]);
+            let r = unsafe { gr_hbond_batch(self.plan, 0, 1, self.cap, d.as_mut_ptr(), h.as_mut_ptr(), a.as_mut_ptr(), dist.as_mut_ptr(), ang.as_mut_ptr(),
+                                            offs.as_mut_ptr(), &mut total, &mut st) };
+            if r != GR_OK { return Err(hbond_error(&self.sys, r, &self.pairs, false)); }
+            if total > self.cap { self.cap = total + total / 4; continue; }
+            return Ok(self.pairs.iter().enumerate().map(|(p, &key)| {
+                let bonds = (offs[p] as usize..offs[p + 1] as usize)
+                    .map(|k| HipHBond { donor: d[k] as usize, hydrogen: h[k] as usize, acceptor: a[k] as usize, distance: dist[k], angle: ang[k] })
+                    .collect();
+                (key, bonds)
+            }).collect());
         }
     }
 }
