@@ -17,7 +17,7 @@ c_i32p = C.POINTER(C.c_int)
 # status codes (include/groan_hip.h)
 (OK, E_NO_BOX, E_NOT_ORTHOGONAL, E_ZERO_BOX, E_EMPTY_GROUP, E_INCONSISTENT_GROUP, E_NO_POSITION, E_NO_MASS,
  E_GROUP_NOT_FOUND, E_OUT_OF_RANGE, E_INVALID_ARG, E_GROUP_EXISTS, E_HIP, E_NO_DEVICE, E_UNSUPPORTED_BOX, E_IO, E_FORMAT,
- E_INVALID_NAME, E_EMPTY_CHAIN, E_NONEXISTENT_CHAIN, E_DUPLICATE_PAIR, E_UNUSED_CHAIN) = range(22)
+ E_INVALID_NAME, E_EMPTY_CHAIN, E_NONEXISTENT_CHAIN, E_DUPLICATE_PAIR, E_UNUSED_CHAIN, E_INVALID_BOND) = range(23)
 
 CENTER_NAIVE, CENTER_ESTIMATE, CENTER_PBC = 0, 1, 2
 
@@ -123,6 +123,16 @@ SIGNATURES = {
     "gr_hbond_plan_destroy": (None, [C.c_void_p]),
     "gr_hbond_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                  c_u64p, C.c_void_p]),
+    "gr_add_bond": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64]),
+    "gr_add_bonds": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    "gr_clear_bonds": (C.c_int, [C.c_void_p]),
+    "gr_has_bonds": (C.c_int, [C.c_void_p]),
+    "gr_mol_references": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, c_u64p]),
+    "gr_molecule_atoms": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, c_u64p]),
+    "gr_make_molecules_whole": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "gr_make_molecules_whole_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "gr_make_group_whole": (C.c_int, [C.c_void_p, C.c_uint32, C.c_char_p]),
+    "gr_make_group_whole_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_void_p]),
     "gr_group_center_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "gr_group_translate_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_void_p, C.c_void_p]),
     "gr_group_wrap_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_void_p]),

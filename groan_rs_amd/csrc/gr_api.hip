@@ -52,6 +52,8 @@ struct Group {
 
 }  // namespace
 
+struct GrWhole;   // bond topology + make-whole state (gr_whole.h), created on first use
+
 struct gr_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -81,6 +83,7 @@ struct gr_ctx {
     std::vector<uint8_t> box9_set;
     std::vector<float> box9_host;     // [n_slots][9]
     std::map<std::string, Group> groups;
+    GrWhole *whole = nullptr;         // bonds, molecules and their device map (gr_whole.h)
     // workspace
     GrCenPartial *cen_partials = nullptr;
     GrAccPartial *acc_partials = nullptr;
@@ -747,6 +750,7 @@ const char *gr_status_string(int s) try {
     case GR_E_NONEXISTENT_CHAIN: return "chain does not exist";
     case GR_E_DUPLICATE_PAIR: return "pair of chains requested multiple times";
     case GR_E_UNUSED_CHAIN: return "not all chains are used";
+    case GR_E_INVALID_BOND: return "invalid bond";
     default: return "unknown status";
     }
 } catch (...) { return nullptr; }
@@ -838,12 +842,15 @@ gr_ctx *gr_ctx_create(int device, uint64_t n_atoms, uint32_t n_slots, int *statu
     return c;
 } catch (...) { return nullptr; }
 
+static void whole_release(gr_ctx *c);   // gr_whole.h
+
 void gr_ctx_destroy(gr_ctx *c) try {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     resident_done(c);
+    whole_release(c);
     for (auto &kv : c->groups) { if (kv.second.idx_dev) (void)hipFree(kv.second.idx_dev); if (kv.second.mask_dev) (void)hipFree(kv.second.mask_dev); }
     if (c->frames) (void)hipFree(c->frames);
     if (c->aos_up) (void)hipFree(c->aos_up);
@@ -3744,3 +3751,4 @@ int gr_synth_uniform(gr_ctx *c, uint32_t slot, const float *box9, uint64_t seed)
 }  // extern "C"
 
 #include "gr_hbonds.h"   // hydrogen bonds: kernels, plan and C ABI (after the context and its helpers)
+#include "gr_whole.h"    // bond topology, make_molecules_whole / make_group_whole: kernels and C ABI

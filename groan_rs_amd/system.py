@@ -11,7 +11,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (OK, E_NO_BOX, E_NOT_ORTHOGONAL, E_ZERO_BOX, E_EMPTY_GROUP, E_INCONSISTENT_GROUP,
-                   E_NO_POSITION, E_NO_MASS, E_GROUP_NOT_FOUND, E_OUT_OF_RANGE, E_GROUP_EXISTS, E_INVALID_NAME)
+                   E_NO_POSITION, E_NO_MASS, E_GROUP_NOT_FOUND, E_OUT_OF_RANGE, E_GROUP_EXISTS, E_INVALID_NAME, E_INVALID_BOND)
 
 
 class Dimension(IntEnum):
@@ -610,6 +610,84 @@ class System:
     def group_translate_batch(self, name, vector, first_slot, n_frames, raise_on_error=True):
         v = np.ascontiguousarray(vector, np.float32); st_arr = np.zeros(n_frames, np.int32)
         st = self._lib.gr_group_translate_batch(self._ctx, first_slot, n_frames, name.encode() if name else None, _ptr(v), _ptr(st_arr))
+        if st != OK and raise_on_error:
+            self._raise_group(st)
+        return st_arr
+
+    # -- bond topology and whole molecules (modifying.rs:235-487, iterating.rs:238-245,399-432; gr_whole.h)
+    def _raise_bond(self, status):
+        if status == E_INVALID_BOND:
+            cnt = (C.c_uint64 * 2)()
+            self._lib.gr_last_error_counts(self._ctx, cnt)
+            raise AtomError("InvalidBond", (int(cnt[0]), int(cnt[1])), status)
+        self._raise_atom(status)
+
+    def add_bond(self, index1, index2):
+        """System::add_bond: AtomError InvalidBond((i, j)) for i == j, then OutOfRange(i), OutOfRange(j)"""
+        st = self._lib.gr_add_bond(self._ctx, int(index1), int(index2))
+        if st != OK:
+            self._raise_bond(st)
+
+    def add_bonds(self, pairs):
+        """add_bond for every (i, j) row of `pairs`, in order; the first bad pair raises and nothing of the call is applied"""
+        p = np.ascontiguousarray(np.asarray(pairs, np.uint64).reshape(-1, 2))
+        st = self._lib.gr_add_bonds(self._ctx, _ptr(p), p.shape[0])
+        if st != OK:
+            self._raise_bond(st)
+
+    def clear_bonds(self):
+        st = self._lib.gr_clear_bonds(self._ctx)
+        if st != OK:
+            self._raise_atom(st)
+
+    def has_bonds(self):
+        return bool(self._lib.gr_has_bonds(self._ctx))
+
+    def get_mol_references(self):
+        """the reference atom (lowest index) of every polyatomic molecule, ascending (create_mol_references)"""
+        n = C.c_uint64(0)
+        st = self._lib.gr_mol_references(self._ctx, None, 0, C.byref(n))
+        out = np.zeros(n.value, np.uint64)
+        if st == OK and n.value:
+            st = self._lib.gr_mol_references(self._ctx, _ptr(out), n.value, C.byref(n))
+        if st != OK:
+            self._raise_atom(st)
+        return [int(x) for x in out]
+
+    def molecule_indices(self, index):
+        """the atoms of the molecule of `index` in molecule_iter order (breadth-first, neighbours ascending)"""
+        n = C.c_uint64(0)
+        st = self._lib.gr_molecule_atoms(self._ctx, int(index), None, 0, C.byref(n))
+        if st != OK:
+            self._raise_atom(st)
+        out = np.zeros(n.value, np.uint64)
+        st = self._lib.gr_molecule_atoms(self._ctx, int(index), _ptr(out), n.value, C.byref(n))
+        if st != OK:
+            self._raise_atom(st)
+        return [int(x) for x in out]
+
+    def make_molecules_whole(self, slot=0):
+        """System::make_molecules_whole on one slot; AtomError as the reference (a failed frame is left untouched)"""
+        st = self._lib.gr_make_molecules_whole(self._ctx, slot)
+        if st != OK:
+            self._raise_atom(st)
+
+    def make_molecules_whole_batch(self, first_slot, n_frames, raise_on_error=True):
+        st_arr = np.zeros(n_frames, np.int32)
+        st = self._lib.gr_make_molecules_whole_batch(self._ctx, first_slot, n_frames, _ptr(st_arr))
+        if st != OK and raise_on_error:
+            self._raise_atom(st)
+        return st_arr
+
+    def make_group_whole(self, name, slot=0):
+        """System::make_group_whole on one slot; GroupError as the reference (a failed frame is left untouched)"""
+        st = self._lib.gr_make_group_whole(self._ctx, slot, name.encode())
+        if st != OK:
+            self._raise_group(st)
+
+    def make_group_whole_batch(self, name, first_slot, n_frames, raise_on_error=True):
+        st_arr = np.zeros(n_frames, np.int32)
+        st = self._lib.gr_make_group_whole_batch(self._ctx, first_slot, n_frames, name.encode(), _ptr(st_arr))
         if st != OK and raise_on_error:
             self._raise_group(st)
         return st_arr

@@ -66,7 +66,8 @@ enum {
     GR_E_EMPTY_CHAIN = 18,       /* HBondError::EmptyChain (errors.rs:675-677); index = chain   */
     GR_E_NONEXISTENT_CHAIN = 19, /* HBondError::NonexistentChain(chain); index = chain          */
     GR_E_DUPLICATE_PAIR = 20,    /* HBondError::PairSpecifiedMultipleTimes; index = ordinal of the repeated pair */
-    GR_E_UNUSED_CHAIN = 21       /* HBondError::UnusedChain                                      */
+    GR_E_UNUSED_CHAIN = 21,      /* HBondError::UnusedChain                                      */
+    GR_E_INVALID_BOND = 22       /* AtomError::InvalidBond(i, j)          errors.rs:295-296; gr_last_error_counts = (i, j) */
 };
 
 /* Dimension (src/structures/dimension.rs:13-23) */
@@ -410,7 +411,7 @@ int gr_group_pairs_within(gr_ctx *ctx, uint32_t slot, const char *group1, const 
 /* ---------------------------------------------------------------- hydrogen bonds over a batch of resident frames
  * HBondAnalysis / HBondTrajRead::hbonds_analyze (src/system/hbonds.rs:154-373).  A plan is built once: `groups` holds
  * n_chains x 3 group names of the context (acceptors, donors, hydrogens of each chain), `pairs` n_pairs x 2 chain indices,
- * `bonds` n_bonds x 2 atom indices (either order; the context has no topology: the caller passes its system's bonds).  A donor
+ * `bonds` n_bonds x 2 atom indices (either order; the plan does not read the context's bonds (gr_add_bond): the caller passes them).  A donor
  * is kept when it is bonded to an atom of its chain's hydrogen group; its hydrogens are taken in index order.  Plan errors, in
  * the reference's order: GR_E_OUT_OF_RANGE (a bonded atom outside the system, index = the atom), per chain GR_E_GROUP_NOT_FOUND
  * and GR_E_EMPTY_CHAIN (index = the chain), then the pairs: GR_E_NONEXISTENT_CHAIN (index = the chain), GR_E_DUPLICATE_PAIR
@@ -434,6 +435,41 @@ gr_hbond_plan *gr_hbond_plan_create(gr_ctx *ctx, const char *const *groups, uint
 void gr_hbond_plan_destroy(gr_hbond_plan *plan);
 int gr_hbond_batch(gr_hbond_plan *plan, uint32_t first_slot, uint32_t n_frames, uint64_t max_bonds, uint32_t *donor, uint32_t *hydrogen,
                    uint32_t *acceptor, float *distance, float *angle, uint64_t *offsets, uint64_t *n_total, int *status_out);
+
+/* ---------------------------------------------------------------- bond topology, whole molecules / groups
+ * The context's bonds (Atom::get_bonded, a sorted container) and what the reference derives from them.  Every bond change resets
+ * the molecules, which are computed again on first use (reset_mol_references, mod.rs:349-377), and the per-atom map the device
+ * reads (uploaded once per topology, not per frame).
+ *   gr_add_bond            System::add_bond (modifying.rs:235-252): i == j is GR_E_INVALID_BOND (counts = (i, j)), checked before
+ *                          GR_E_OUT_OF_RANGE of i, then of j (gr_last_error_index = the index); a bond that exists is kept once
+ *   gr_add_bonds           pairs[n_pairs][2] in order; on the first bad pair nothing of the call is applied
+ *   gr_clear_bonds         System::clear_bonds (modifying.rs:480-487); gr_has_bonds: System::has_bonds (mod.rs:437), 1 or 0
+ *   gr_mol_references      what create_mol_references yields (modifying.rs:258-283): the lowest atom of every polyatomic molecule,
+ *                          ascending; *n = their number, at most `cap` are written (out may be NULL to count)
+ *   gr_molecule_atoms      molecule_iter (iterating.rs:238-245,399-432): breadth-first from `index`, neighbours ascending; an atom
+ *                          without bonds yields itself; GR_E_OUT_OF_RANGE for index >= n_atoms
+ *   gr_make_molecules_whole  System::make_molecules_whole (modifying.rs:338-392): every reference atom wrapped into the box, every
+ *                          other atom of its molecule placed at ref_w + vector_to(ref_w, p); atoms outside polyatomic molecules are
+ *                          never touched.  Errors: the box (GR_E_NO_BOX / GR_E_ZERO_BOX / GR_E_NOT_ORTHOGONAL in strict mode /
+ *                          GR_E_UNSUPPORTED_BOX, even without bonds), then GR_E_NO_POSITION with the atom the reference stops on:
+ *                          of the molecules holding an atom without position the one with the lowest reference, in it the reference
+ *                          when it has no position, else the first such atom in breadth-first order.
+ *   gr_make_group_whole    System::make_group_whole (modifying.rs:447-475): c = group_estimate_center, then every atom of the group
+ *                          becomes c + vector_to(c, p); the errors are exactly those of gr_group_center(.., GR_CENTER_ESTIMATE, 0, ..)
+ * A frame that fails is left bit for bit untouched -- unlike the reference, which has already moved the molecules before the
+ * failing one.  The _batch forms take n_frames consecutive slots and follow the batch rules below (status_out may be NULL; the
+ * return value is the first failed frame's status, message and gr_last_error_index).  Non-orthogonal cells outside strict mode
+ * use the library's triclinic wrap and vector_to, as every other call. */
+int gr_add_bond(gr_ctx *ctx, uint64_t i, uint64_t j);                                            /* modifying.rs:235-252 */
+int gr_add_bonds(gr_ctx *ctx, const uint64_t *pairs, uint64_t n_pairs);
+int gr_clear_bonds(gr_ctx *ctx);                                                                 /* modifying.rs:480-487 */
+int gr_has_bonds(const gr_ctx *ctx);                                                             /* mod.rs:437 */
+int gr_mol_references(gr_ctx *ctx, uint64_t *out, uint64_t cap, uint64_t *n);                    /* modifying.rs:258-283 */
+int gr_molecule_atoms(gr_ctx *ctx, uint64_t index, uint64_t *out, uint64_t cap, uint64_t *n);    /* iterating.rs:238-245,399-432 */
+int gr_make_molecules_whole(gr_ctx *ctx, uint32_t slot);                                         /* modifying.rs:338-392 */
+int gr_make_molecules_whole_batch(gr_ctx *ctx, uint32_t first_slot, uint32_t n_frames, int *status_out);
+int gr_make_group_whole(gr_ctx *ctx, uint32_t slot, const char *group);                          /* modifying.rs:447-475 */
+int gr_make_group_whole_batch(gr_ctx *ctx, uint32_t first_slot, uint32_t n_frames, const char *group, int *status_out);
 
 /* ---------------------------------------------------------------- per-frame analyses over a batch of slots
  * The calls above for `n_frames` consecutive slots in ONE set of launches and one read-back (a trajectory loop of

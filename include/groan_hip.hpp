@@ -210,6 +210,47 @@ class System {
     void atoms_center(const std::string &g, Dimension dim, uint32_t slot = 0) { int st = gr_atoms_center(ctx_, slot, g.c_str(), (int)dim, 0); if (st) group_error(st, g); }
     void atoms_center_mass(const std::string &g, Dimension dim, uint32_t slot = 0) { int st = gr_atoms_center(ctx_, slot, g.c_str(), (int)dim, 1); if (st) group_error(st, g); }
 
+    // bond topology and whole molecules: modifying.rs:235-487, iterating.rs:238-245,399-432 (a failed frame is left untouched)
+    void add_bond(uint64_t i, uint64_t j) { int st = gr_add_bond(ctx_, i, j); if (st) bond_error(st); }
+    void add_bonds(const std::vector<std::pair<uint64_t, uint64_t>> &pairs) {
+        std::vector<uint64_t> flat;
+        flat.reserve(2 * pairs.size());
+        for (const auto &p : pairs) { flat.push_back(p.first); flat.push_back(p.second); }
+        int st = gr_add_bonds(ctx_, flat.data(), pairs.size());
+        if (st) bond_error(st);
+    }
+    void clear_bonds() { check_plain(gr_clear_bonds(ctx_)); }
+    bool has_bonds() const { return gr_has_bonds(ctx_) != 0; }
+    std::vector<uint64_t> get_mol_references() {
+        uint64_t n = 0;
+        check_plain(gr_mol_references(ctx_, nullptr, 0, &n));
+        std::vector<uint64_t> out(n);
+        check_plain(gr_mol_references(ctx_, out.data(), n, &n));
+        return out;
+    }
+    std::vector<uint64_t> molecule_indices(uint64_t index) {
+        uint64_t n = 0;
+        int st = gr_molecule_atoms(ctx_, index, nullptr, 0, &n);
+        if (st) atom_error(st);
+        std::vector<uint64_t> out(n);
+        st = gr_molecule_atoms(ctx_, index, out.data(), n, &n);
+        if (st) atom_error(st);
+        return out;
+    }
+    void make_molecules_whole(uint32_t slot = 0) { int st = gr_make_molecules_whole(ctx_, slot); if (st) atom_error(st); }
+    // per-frame statuses in *status (may be NULL); throws for the first failed frame unless status is given
+    void make_molecules_whole_batch(uint32_t first_slot, uint32_t n_frames, std::vector<int> *status = nullptr) {
+        if (status) status->assign(n_frames, GR_OK);
+        int st = gr_make_molecules_whole_batch(ctx_, first_slot, n_frames, status ? status->data() : nullptr);
+        if (st && !status) atom_error(st);
+    }
+    void make_group_whole(const std::string &g, uint32_t slot = 0) { int st = gr_make_group_whole(ctx_, slot, g.c_str()); if (st) group_error(st, g); }
+    void make_group_whole_batch(const std::string &g, uint32_t first_slot, uint32_t n_frames, std::vector<int> *status = nullptr) {
+        if (status) status->assign(n_frames, GR_OK);
+        int st = gr_make_group_whole_batch(ctx_, first_slot, n_frames, g.c_str(), status ? status->data() : nullptr);
+        if (st && !status) group_error(st, g);
+    }
+
     // rmsd.rs:75-166
     float calc_rmsd(const System &reference, const std::string &group, uint32_t slot = 0, uint32_t ref_slot = 0) const {
         float r = 0;
@@ -255,6 +296,10 @@ class System {
         case GR_E_NO_BOX: case GR_E_NOT_ORTHOGONAL: case GR_E_ZERO_BOX: throw Error("GroupError", "InvalidSimBox(" + simbox_variant(st) + ")", st);
         default: throw Error("DeviceError", std::string(gr_status_string(st)) + ": " + gr_last_error(ctx_) + " [" + g + "]", st);
         }
+    }
+    [[noreturn]] void bond_error(int st) const {
+        if (st == GR_E_INVALID_BOND) { uint64_t c[2]; gr_last_error_counts(ctx_, c); throw Error("AtomError", "InvalidBond", st, 0, c[0], c[1]); }
+        atom_error(st);
     }
     [[noreturn]] void atom_error(int st) const {
         uint64_t idx = gr_last_error_index(ctx_);

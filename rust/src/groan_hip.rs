@@ -32,6 +32,7 @@ pub const GR_E_EMPTY_CHAIN: c_int = 18;
 pub const GR_E_NONEXISTENT_CHAIN: c_int = 19;
 pub const GR_E_DUPLICATE_PAIR: c_int = 20;
 pub const GR_E_UNUSED_CHAIN: c_int = 21;
+pub const GR_E_INVALID_BOND: c_int = 22;
 
 #[repr(C)] pub struct gr_hbond_plan { _private: [u8; 0] }
 #[repr(C)] pub struct gr_pool { _private: [u8; 0] }
@@ -120,6 +121,17 @@ extern "C" {
     pub fn gr_group_translate_batch(ctx: *mut gr_ctx, first_slot: u32, n_frames: u32, group: *const c_char, v: *const c_float, status: *mut c_int) -> c_int;
     pub fn gr_group_wrap_batch(ctx: *mut gr_ctx, first_slot: u32, n_frames: u32, group: *const c_char, status: *mut c_int) -> c_int;
     pub fn gr_atoms_center_batch(ctx: *mut gr_ctx, first_slot: u32, n_frames: u32, ref_group: *const c_char, dim: c_int, weighted: c_int, status: *mut c_int) -> c_int;
+    // bond topology and whole molecules (modifying.rs:235-487, iterating.rs:238-245,399-432)
+    pub fn gr_add_bond(ctx: *mut gr_ctx, i: u64, j: u64) -> c_int;
+    pub fn gr_add_bonds(ctx: *mut gr_ctx, pairs: *const u64, n_pairs: u64) -> c_int;
+    pub fn gr_clear_bonds(ctx: *mut gr_ctx) -> c_int;
+    pub fn gr_has_bonds(ctx: *const gr_ctx) -> c_int;
+    pub fn gr_mol_references(ctx: *mut gr_ctx, out: *mut u64, cap: u64, n: *mut u64) -> c_int;
+    pub fn gr_molecule_atoms(ctx: *mut gr_ctx, index: u64, out: *mut u64, cap: u64, n: *mut u64) -> c_int;
+    pub fn gr_make_molecules_whole(ctx: *mut gr_ctx, slot: u32) -> c_int;
+    pub fn gr_make_molecules_whole_batch(ctx: *mut gr_ctx, first_slot: u32, n_frames: u32, status: *mut c_int) -> c_int;
+    pub fn gr_make_group_whole(ctx: *mut gr_ctx, slot: u32, group: *const c_char) -> c_int;
+    pub fn gr_make_group_whole_batch(ctx: *mut gr_ctx, first_slot: u32, n_frames: u32, group: *const c_char, status: *mut c_int) -> c_int;
     pub fn gr_ctx_set_tuning(ctx: *mut gr_ctx, key: c_int, value: i64) -> c_int;   // GR_TUNE_* (include/groan_hip.h)
     pub fn gr_host_alloc(bytes: usize) -> *mut c_void;                              // pinned memory: asynchronous gr_frame_upload
     pub fn gr_host_free(p: *mut c_void);
@@ -232,6 +244,80 @@ impl HipSystem {
         match unsafe { gr_group_distance(self.ctx, slot, a.as_ptr(), b.as_ptr(), dim as c_int, &mut out) } {
             GR_OK => Ok(out),
             s => Err(self.group_error(s, g1)),
+        }
+    }
+}
+
+/// Bond topology and whole molecules on the device (`System::add_bond` / `clear_bonds` / `has_bonds` / `make_molecules_whole` /
+/// `make_group_whole`, src/system/modifying.rs:235-487).  Copy the system's bonds once with `add_bonds`; a frame that fails is
+/// left untouched (the reference has already moved the molecules before the failing one).
+impl HipSystem {
+    fn bond_error(&self, status: c_int) -> AtomError {
+        if status == GR_E_INVALID_BOND {
+            let mut c = [0u64; 2];
+            unsafe { gr_last_error_counts(self.ctx, c.as_mut_ptr()) };
+            return AtomError::InvalidBond(c[0] as usize, c[1] as usize);
+        }
+        self.atom_error(status)
+    }
+    pub fn add_bond(&self, i: usize, j: usize) -> Result<(), AtomError> {
+        match unsafe { gr_add_bond(self.ctx, i as u64, j as u64) } { GR_OK => Ok(()), s => Err(self.bond_error(s)) }
+    }
+    /// the bonds of `system` (each once, i < j), e.g. after `add_bonds_from_pdb`
+    pub fn add_bonds_from(&self, system: &System) -> Result<(), AtomError> {
+        let mut flat: Vec<u64> = Vec::new();
+        for atom in system.atoms_iter() {
+            for j in atom.get_bonded().iter() {
+                if atom.get_index() < j { flat.push(atom.get_index() as u64); flat.push(j as u64); }
+            }
+        }
+        match unsafe { gr_add_bonds(self.ctx, flat.as_ptr(), (flat.len() / 2) as u64) } { GR_OK => Ok(()), s => Err(self.bond_error(s)) }
+    }
+    pub fn clear_bonds(&self) { unsafe { gr_clear_bonds(self.ctx) }; }
+    pub fn has_bonds(&self) -> bool { unsafe { gr_has_bonds(self.ctx) != 0 } }
+    pub fn get_mol_references(&self) -> Vec<usize> {
+        let mut n = 0u64;
+        unsafe { gr_mol_references(self.ctx, std::ptr::null_mut(), 0, &mut n) };
+        let mut out = vec![0u64; n as usize];
+        unsafe { gr_mol_references(self.ctx, out.as_mut_ptr(), n, &mut n) };
+        out.into_iter().map(|x| x as usize).collect()
+    }
+    /// `molecule_iter(index)` order (iterating.rs:399-432)
+    pub fn molecule_indices(&self, index: usize) -> Result<Vec<usize>, AtomError> {
+        let mut n = 0u64;
+        let st = unsafe { gr_molecule_atoms(self.ctx, index as u64, std::ptr::null_mut(), 0, &mut n) };
+        if st != GR_OK { return Err(self.atom_error(st)); }
+        let mut out = vec![0u64; n as usize];
+        unsafe { gr_molecule_atoms(self.ctx, index as u64, out.as_mut_ptr(), n, &mut n) };
+        Ok(out.into_iter().map(|x| x as usize).collect())
+    }
+    pub fn make_molecules_whole(&self, slot: u32) -> Result<(), AtomError> {
+        match unsafe { gr_make_molecules_whole(self.ctx, slot) } { GR_OK => Ok(()), s => Err(self.atom_error(s)) }
+    }
+    /// per-frame results of `n_frames` consecutive slots (one set of launches, one read-back)
+    pub fn make_molecules_whole_batch(&self, first_slot: u32, n_frames: u32) -> Vec<Result<(), AtomError>> {
+        let mut st = vec![0 as c_int; n_frames as usize];
+        unsafe { gr_make_molecules_whole_batch(self.ctx, first_slot, n_frames, st.as_mut_ptr()) };
+        st.into_iter().map(|s| if s == GR_OK { Ok(()) } else { Err(self.atom_error_plain(s)) }).collect()
+    }
+    pub fn make_group_whole(&self, slot: u32, name: &str) -> Result<(), GroupError> {
+        let cname = CString::new(name).unwrap();
+        match unsafe { gr_make_group_whole(self.ctx, slot, cname.as_ptr()) } { GR_OK => Ok(()), s => Err(self.group_error(s, name)) }
+    }
+    /// the per-frame statuses (GR_OK or the frame's error); Err for the call-level group errors
+    pub fn make_group_whole_batch(&self, first_slot: u32, n_frames: u32, name: &str) -> Result<Vec<c_int>, GroupError> {
+        let cname = CString::new(name).unwrap();
+        let mut st = vec![0 as c_int; n_frames as usize];
+        match unsafe { gr_make_group_whole_batch(self.ctx, first_slot, n_frames, cname.as_ptr(), st.as_mut_ptr()) } {
+            s @ (GR_E_GROUP_NOT_FOUND | GR_E_EMPTY_GROUP) => Err(self.group_error(s, name)),
+            _ => Ok(st),
+        }
+    }
+    /// a frame's status without its atom index (only the first failed frame's index is kept by the library)
+    fn atom_error_plain(&self, status: c_int) -> AtomError {
+        match status {
+            GR_E_NO_POSITION => AtomError::InvalidPosition(PositionError::NoPosition(usize::MAX)),
+            s => AtomError::InvalidSimBox(simbox_err(s)),
         }
     }
 }
