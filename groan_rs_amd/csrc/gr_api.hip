@@ -128,7 +128,15 @@ struct gr_ctx {
     unsigned long long *res_wgrec = nullptr; size_t res_wgrec_cap = 0;   // [frames][streaming workgroups, padded to 16][32] tagged words
     unsigned long long *res_rec = nullptr;   // [GR_MAX_BATCH][16]
     uint32_t *res_abort = nullptr;    // device word
-    uint32_t *res_words_host = nullptr;   // pinned: the three control words of the last resident launch, copied behind it on the stream
+    uint32_t *res_words_host = nullptr;   // the control words of the last resident launch as res_collect took them out of res_out (8, 9: this launch's share)
+    // what k_res_close hands back behind a resident launch, in host-mapped coherent memory: the frames' closed states, the launch's control
+    // words and -- stored last -- the call's sequence number, which the host polls (res_wait) instead of synchronising the stream
+    struct ResOut { GrFrameState st[GR_MAX_BATCH]; uint32_t words[16]; alignas(64) uint32_t seq; };
+    ResOut *res_out = nullptr, *res_out_dev = nullptr;   // the block and its device address
+    uint32_t res_seq = 0;             // sequence number of the last k_res_close
+    uint32_t res_checkin = 0, res_closed = 0;   // running totals on the device, modulo 2^32: workgroups that have checked in (res_abort[1]), frames exported (res_abort[12])
+    uint32_t res_late_seen[2] = { 0, 0 };       // res_abort[8], [9] (running sums) as the last launch left them
+    uint64_t res_lean_segments = 0, res_sync_fallbacks = 0;   // gr_ctx_stat: resident launches that started from fresh states; polls that gave up and synchronised the stream
     GrShapeSet *shape_set_dev = nullptr;      // the shapes of the geometry selection in flight (k_shape_mask reads them through a uniform pointer)
     unsigned long long *shape_mask_dev = nullptr, *shape_mask_host = nullptr; size_t shape_mask_cap = 0;   // geometry selection: one bit per atom of the source group (device, pinned host), grown on demand
     uint32_t res_epoch = 0;
@@ -197,6 +205,7 @@ struct Pending {   // a segment between gr_rmsd_batch_begin and gr_rmsd_batch_en
     uint64_t group_n = 0;
     bool has_group = false;
     bool small = false; uint32_t small_seq = 0;   // the segment is one single-wave dispatch (gr_small.h): segment_end polls the mapped word
+    uint32_t res_seq = 0, res_epoch = 0; bool res_fresh = false;   // (resident launch: its k_res_close's sequence number, its epoch, started from fresh states)
 #ifdef GR_EXP_TIMELINE
     unsigned long long *tl_dev = nullptr;
 #endif
@@ -640,6 +649,63 @@ static int small_wait(gr_ctx *c, uint32_t seq, uint32_t words = 1) {
     return GR_OK;
 }
 
+// The resident pass (gr_resident.h) between launches.  res_next_epoch: the tag of the next launch's words; 32 bits, so after 2^32 launches
+// every tagged word is cleared and the count starts again at 1 -- a word can then never carry the tag of a launch 2^32 launches ago.
+static int res_next_epoch(gr_ctx *c, uint32_t *epoch) {
+    if (++c->res_epoch == 0u) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (c->res_wgrec) HIPCHK(c, hipMemset(c->res_wgrec, 0, c->res_wgrec_cap * sizeof(unsigned long long)));
+        HIPCHK(c, hipMemset(c->res_rec, 0, (size_t)GR_MAX_BATCH * 16 * sizeof(unsigned long long)));
+        HIPCHK(c, hipMemset(c->res_abort + 2, 0, 2 * sizeof(uint32_t)));
+        c->res_epoch = 1u;
+    }
+    *epoch = c->res_epoch;
+    return GR_OK;
+}
+// tests (GR_TUNE_TEST_RESIDENT_NO_START): the launch of this epoch finds its start verdict already "never started"
+static int res_test_no_start(gr_ctx *c, uint32_t epoch) {
+    if (!c->res_test_no_start) return GR_OK;
+    const unsigned long long two = 2ull | ((unsigned long long)epoch << 32);
+    c->res_test_no_start = 0;
+    HIPCHK(c, hipMemcpyAsync(c->res_abort + 2, &two, sizeof two, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return GR_OK;
+}
+// k_res_close behind a resident launch of `nb` frames; returns the sequence number to wait for in *seq
+template <int MODE>
+static int res_close(gr_ctx *c, uint32_t nb, const double *fit_partials, uint32_t nparts, double sum_w, uint32_t epoch, bool fresh, uint32_t *seq) {
+    const uint32_t sq = c->res_seq + 1u;
+    k_res_close<MODE><<<dim3(nb), dim3(64), 0, c->stream>>>(fit_partials, nparts, sum_w, c->state_dev, c->res_rec, epoch, fresh ? 1u : 0u, c->res_abort, c->res_closed + nb,
+                                                        c->res_out_dev->st, c->res_out_dev->words, &c->res_out_dev->seq, sq);
+    HIPCHK(c, hipGetLastError());
+    c->res_seq = sq; c->res_closed += nb; *seq = sq;
+    return GR_OK;
+}
+// wait for k_res_close's sequence word as small_wait does (spin for up to ~20 ms of wall clock, then the stream synchronisation decides) and
+// take the launch's results out of the mapped block: the frames' states into c->state_host, the control words into c->res_words_host --
+// words 8 and 9 as THIS launch's share of the running sums.  `started`: the launch's start handshake opened it.
+static int res_collect(gr_ctx *c, uint32_t seq, uint32_t nb, uint32_t epoch, bool *started) {
+    volatile uint32_t *w = &c->res_out->seq;
+    const auto t0 = std::chrono::steady_clock::now();
+    for (uint32_t spins = 0; *w != seq; ++spins) {
+        if ((spins & 1023u) == 1023u && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(20)) {
+            // (a launch of many frames takes longer than that: the stream synchronisation is then simply the wait it always was)
+            c->res_sync_fallbacks++;
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            if (*w != seq) return fail(c, GR_E_HIP, "the kernel behind the resident pass ended without publishing its results");
+            break;
+        }
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    memcpy(c->state_host, c->res_out->st, (size_t)nb * sizeof(GrFrameState));
+    memcpy(c->res_words_host, c->res_out->words, 12 * sizeof(uint32_t));
+    for (int k = 0; k < 2; ++k) { const uint32_t v = c->res_words_host[8 + k]; c->res_words_host[8 + k] = v - c->res_late_seen[k]; c->res_late_seen[k] = v; }
+    *started = c->res_words_host[2] == 1u && c->res_words_host[3] == epoch;
+    // the rare ends -- never started, aborted -- go on as they always have: on an idle stream
+    if (!*started || c->res_words_host[0]) HIPCHK(c, hipStreamSynchronize(c->stream));
+    return GR_OK;
+}
+
 // launch one centre stage (sums + finalize) for `nf` frames starting at first_slot
 int center_stage(gr_ctx *c, uint32_t first_slot, uint32_t nf, const GrSel &sel, int kind, int weighted,
                  int mass_first, int target, int only_status = 0) {
@@ -804,6 +870,9 @@ gr_ctx *gr_ctx_create(int device, uint64_t n_atoms, uint32_t n_slots, int *statu
     ok = ok && hipEventCreate(&c->ev0) == hipSuccess && hipEventCreate(&c->ev1) == hipSuccess;
     ok = ok && hipMalloc(&c->res_abort, 96 * sizeof(uint32_t)) == hipSuccess;
     ok = ok && hipHostMalloc(&c->res_words_host, 16 * sizeof(uint32_t), hipHostMallocDefault) == hipSuccess;
+    ok = ok && hipHostMalloc(reinterpret_cast<void **>(&c->res_out), sizeof(gr_ctx::ResOut), hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess;
+    ok = ok && hipHostGetDevicePointer(reinterpret_cast<void **>(&c->res_out_dev), c->res_out, 0) == hipSuccess && c->res_out_dev != nullptr;
+    if (ok) memset(c->res_out, 0, sizeof(gr_ctx::ResOut));
     ok = ok && hipMemset(c->res_abort, 0, 96 * sizeof(uint32_t)) == hipSuccess;
     ok = ok && hipMalloc(&c->res_rec, (size_t)GR_MAX_BATCH * 16 * sizeof(unsigned long long)) == hipSuccess;
     ok = ok && hipMemset(c->res_rec, 0, (size_t)GR_MAX_BATCH * 16 * sizeof(unsigned long long)) == hipSuccess;
@@ -864,6 +933,7 @@ void gr_ctx_destroy(gr_ctx *c) try {
     if (c->fuse_cnt) (void)hipFree(c->fuse_cnt);
     if (c->res_abort) (void)hipFree(c->res_abort);
     if (c->res_words_host) (void)hipHostFree(c->res_words_host);
+    if (c->res_out) (void)hipHostFree(c->res_out);
     if (c->shape_set_dev) (void)hipFree(c->shape_set_dev);
     if (c->shape_mask_dev) (void)hipFree(c->shape_mask_dev);
     if (c->shape_mask_host) (void)hipHostFree(c->shape_mask_host);
@@ -1783,7 +1853,7 @@ int gr_group_center_batch(gr_ctx *c, uint32_t first_slot, uint32_t n_frames, con
 // `torn[f]` = 1: an aborted launch left the frame half-moved (reported as GR_E_HIP, as the RMSD-fit form does);
 // `ran`: the launch started, so state_dev holds what its finalizers wrote (GR_ST_FALLBACK / GR_ST_ABORTED for the frames handed back).
 static int center_resident(gr_ctx *c, uint32_t s0, uint32_t nb, const GrSel &all, const GrSel &csel, int dim_mask, int weighted,
-                           const std::vector<int> &pre, std::vector<uint8_t> &done, std::vector<uint8_t> &torn, bool &ran) {
+                           const std::vector<int> &pre, bool fresh_states, std::vector<uint8_t> &done, std::vector<uint8_t> &torn, bool &ran) {
     done.assign(nb, 0); torn.assign(nb, 0); ran = false;
     if (!c->center_resident || !csel.contiguous || csel.masked || !all.contiguous || all.start != 0 || all.n != c->n) return GR_OK;
     // which groups: the launch costs the same whatever the group -- 4.25 us per 1e6-atom frame in an orthorhombic cell, 4.35-4.4 in others -- while
@@ -1814,7 +1884,9 @@ static int center_resident(gr_ctx *c, uint32_t s0, uint32_t nb, const GrSel &all
     }
     GrResCtl ctl;
     memset(&ctl, 0, sizeof ctl);
-    ctl.wgrec = c->res_wgrec; ctl.rec = c->res_rec; ctl.abort = c->res_abort; ctl.progress = c->res_progress; ctl.epoch = ++c->res_epoch; ctl.n_stream = res_stream; ctl.n_fin = n_fin;
+    { const int se = res_next_epoch(c, &ctl.epoch); if (se) return se; }
+    ctl.wgrec = c->res_wgrec; ctl.rec = c->res_rec; ctl.abort = c->res_abort; ctl.progress = c->res_progress; ctl.n_stream = res_stream; ctl.n_fin = n_fin;
+    ctl.checkin_target = c->res_checkin + res_stream + n_fin; ctl.fresh_states = fresh_states ? 1u : 0u;
     ctl.wgs_frame = wgs; ctl.streams = streams; ctl.groups_wg = gwg;
     ctl.team_waves = resident_team_waves(wgs, streams);
     ctl.patience_ticks = (unsigned long long)c->wall_khz * 3000ull; ctl.start_ticks = (unsigned long long)c->wall_khz * 200ull;   // 3 s, 0.2 s
@@ -1830,19 +1902,19 @@ static int center_resident(gr_ctx *c, uint32_t s0, uint32_t nb, const GrSel &all
     bool ubox = true;
     for (uint32_t f = 1; f < nb && ubox; ++f) ubox = memcmp(&c->boxes_host[s0 + f], &c->boxes_host[s0], sizeof(GrBox)) == 0;
     const bool fit_last = c->res_fit_last ? c->res_fit_last == 2 : (uint64_t)res_stream * 10u >= (uint64_t)c->res_max_wgs * 9u;
-    k_res_prepare<<<dim3((res_stream * 8 + 255) / 256), dim3(256), 0, S>>>(c->res_abort + 1, c->res_progress, res_stream * 8);
-    HIPCHK(c, hipGetLastError());
-    if (c->res_test_no_start) { const uint32_t two = 2u; c->res_test_no_start = 0; HIPCHK(c, hipMemcpyAsync(c->res_abort + 2, &two, sizeof two, hipMemcpyHostToDevice, S)); HIPCHK(c, hipStreamSynchronize(S)); }
+    { const int sn = res_test_no_start(c, ctl.epoch); if (sn) return sn; }
     if (hipLaunchKernel(resident_center_fn(ubox, fit_last), dim3(res_stream + n_fin), dim3(GrResShape::LANES), args, GrResShape::LDS_BYTES, S) != hipSuccess) {
         (void)hipGetLastError();          // nothing ran: the two passes take the batch
         c->res_max_wgs = 0;
         return GR_OK;
     }
-    HIPCHK(c, hipMemcpyAsync(c->res_words_host, c->res_abort, 12 * sizeof(uint32_t), hipMemcpyDeviceToHost, S));
-    HIPCHK(c, hipMemcpyAsync(c->state_host, c->state_dev, nb * sizeof(GrFrameState), hipMemcpyDeviceToHost, S));
-    HIPCHK(c, hipStreamSynchronize(S));
+    c->res_checkin += res_stream + n_fin;
+    // the states and control words come back through mapped memory behind the launch (k_res_close); the host polls for them
+    uint32_t seq = 0; bool started = false;
+    { const int sc = res_close<1>(c, nb, nullptr, 0u, 1.0, ctl.epoch, fresh_states, &seq); if (sc) return sc; }
+    { const int sc = res_collect(c, seq, nb, ctl.epoch, &started); if (sc) return sc; }
     c->res_last_streams = streams;
-    if (c->res_words_host[2] != 1u) {      // the launch never started (the device is shared): nothing was touched; sit out the next batches
+    if (!started) {      // the launch never started (the device is shared): nothing was touched; sit out the next batches
         c->res_handshake_misses++;
         c->res_backoff = c->res_backoff ? std::min<uint32_t>(c->res_backoff * 2u, 1024u) : 4u;
         c->res_skip = c->res_backoff;
@@ -1850,6 +1922,7 @@ static int center_resident(gr_ctx *c, uint32_t s0, uint32_t nb, const GrSel &all
     }
     c->res_backoff = 0;
     c->cen_res_launches++;
+    if (fresh_states) c->res_lean_segments++;
     ran = true;
 #ifdef GR_EXP_STEPTIME
     if (getenv("GR_STEPTIME")) {
@@ -1946,12 +2019,16 @@ static int translate_batch_api(gr_ctx *c, uint32_t first_slot, uint32_t n_frames
         std::vector<int> pre; std::vector<std::string> msg;
         batch_prechecks(c, s0, nb, true, pre, msg);
         SlotUse use(c, s0, nb);
-        st = states_from_prechecks(c, nb, pre); if (st) return st;
+        // (where every frame passed the checks and the resident pass may take the batch, the states are not zeroed for it: its finalizers
+        //  start from fresh ones; the two passes below get theirs when it turns out that they run)
+        bool states_unset = cg != nullptr;
+        for (uint32_t f = 0; f < nb; ++f) states_unset = states_unset && pre[f] == GR_OK;
+        if (!states_unset) { st = states_from_prechecks(c, nb, pre); if (st) return st; }
         // atoms_center of the whole system about a large group: one pass over HBM where the resident pass takes it (center_resident); the frames
         // it did not finish -- all of them when it was not taken -- go through the two passes below, one run of consecutive frames at a time
         std::vector<uint8_t> done(nb, 0), torn(nb, 0);
         bool ran = false;
-        if (cg) { st = center_resident(c, s0, nb, make_sel(*g), make_sel(*cg), mask[dim], weighted, pre, done, torn, ran); if (st) return st; }
+        if (cg) { st = center_resident(c, s0, nb, make_sel(*g), make_sel(*cg), mask[dim], weighted, pre, states_unset, done, torn, ran); if (st) return st; }
         bool any_done = false;
         for (uint32_t f = 0; f < nb; ++f) any_done = any_done || done[f];
         if (any_done) {
@@ -1979,7 +2056,7 @@ static int translate_batch_api(gr_ctx *c, uint32_t first_slot, uint32_t n_frames
             continue;
         }
         // (a launch that handed every frame back left its internal statuses in state_dev: the two passes start from the prechecks again)
-        if (ran) { st = states_from_prechecks(c, nb, pre); if (st) return st; }
+        if (ran || states_unset) { st = states_from_prechecks(c, nb, pre); if (st) return st; }
         if (cg) { st = center_stage(c, s0, nb, make_sel(*cg), 1, weighted, 1, 0); if (st) return st; }   // group_estimate_center / _com per frame
         st = translate_batch(c, s0, nb, g, v, cg ? 1 : 2, cg ? mask[dim] : 7, pre, msg, status_out ? status_out + b0 : nullptr, first_err, first_msg, first_idx);
         if (st) return st;
@@ -2098,6 +2175,8 @@ int gr_ctx_stat(const gr_ctx *c, int key, uint64_t *value) {
     case GR_STAT_RES_SCLK_MHZ: *value = c->res_sclk_mhz; return GR_OK;
     case GR_STAT_CENTER_RES_LAUNCHES: *value = c->cen_res_launches; return GR_OK;
     case GR_STAT_CENTER_RES_REDONE: *value = c->cen_res_redone; return GR_OK;
+    case GR_STAT_RES_LEAN_SEGMENTS: *value = c->res_lean_segments; return GR_OK;
+    case GR_STAT_RES_SYNC_FALLBACKS: *value = c->res_sync_fallbacks; return GR_OK;
     default: return GR_E_INVALID_ARG;
     }
 }
@@ -2201,19 +2280,24 @@ static int segment_begin(gr_rmsd_plan *p, uint32_t s0, uint32_t nb, int fit) {
         HIPCHK(c, hipGetLastError());
         return GR_OK;
     }
+    bool states_unset = false;   // every frame passed the host's checks and state_dev has not been zeroed yet
     {
         // the frames' states start from the host-side checks.  When every frame passed them -- the usual case -- the states are zeroed by a
         // kernel: the copy of nb records out of pinned memory costs ~30 us of host time BEFORE the first kernel of the segment can be
         // queued (rocprofv3 --hip-trace of bench.py: hipMemcpyAsync 29 us per call), i.e. with the device idle
+        // ... and not even that where the resident pass takes the segment: its finalizers start from a fresh state of their own
+        // (GrResCtl::fresh_states), so the zeroing waits until the path is known (zero_states)
         bool all_ok = true;
         for (uint32_t f = 0; f < nb; ++f) all_ok = all_ok && q.pre[f] == GR_OK;
-        if (all_ok) { const int sr = state_reset(c, nb); if (sr) return sr; }
-        else {
+        states_unset = all_ok;
+        if (!all_ok) {
             for (uint32_t f = 0; f < nb; ++f) { GrFrameState z = {}; z.err_index = GR_NOIDX; z.status = q.pre[f]; c->state_host[f] = z; }
             HIPCHK(c, hipMemcpyAsync(c->state_dev, c->state_host, nb * sizeof(GrFrameState), hipMemcpyHostToDevice, c->stream));
         }
     }
+    auto zero_states = [&]() -> int { if (!states_unset) return GR_OK; states_unset = false; return state_reset(c, nb); };
     int st;
+    if (!(q.consistent && !p->exact && !small)) { st = zero_states(); if (st) return st; }   // (every path but the one that may end in the resident pass)
     if (small) {
         // ... and a batch of frames of such a selection: the same kernel, one wave per frame (a batch equals its per-frame calls bit for bit)
         k_rmsd_small<0><<<dim3(nb), dim3(64), 0, c->stream>>>(c->frames, c->frame_stride, s0, c->masses, sel, c->boxes_dev, p->dev, c->state_dev, 1, nullptr, nullptr, 0u);
@@ -2283,7 +2367,9 @@ static int segment_begin(gr_rmsd_plan *p, uint32_t s0, uint32_t nb, int fit) {
                 c->res_wgrec_cap = rec_words;
             }
             GrResCtl ctl;
-            ctl.wgrec = c->res_wgrec; ctl.rec = c->res_rec; ctl.abort = c->res_abort; ctl.progress = c->res_progress; ctl.epoch = ++c->res_epoch; ctl.n_stream = res_stream; ctl.n_fin = n_fin;
+            st = res_next_epoch(c, &ctl.epoch); if (st) return st;
+            ctl.wgrec = c->res_wgrec; ctl.rec = c->res_rec; ctl.abort = c->res_abort; ctl.progress = c->res_progress; ctl.n_stream = res_stream; ctl.n_fin = n_fin;
+            ctl.checkin_target = c->res_checkin + res_stream + n_fin; ctl.fresh_states = states_unset ? 1u : 0u;
             ctl.wgs_frame = res_wgs; ctl.streams = res_streams; ctl.groups_wg = res_gwg;
             ctl.team_waves = resident_team_waves(res_wgs, res_streams);
             ctl.patience_ticks = (unsigned long long)c->wall_khz * 3000ull; ctl.start_ticks = (unsigned long long)c->wall_khz * 200ull;   // 3 s, 0.2 s
@@ -2339,10 +2425,8 @@ static int segment_begin(gr_rmsd_plan *p, uint32_t s0, uint32_t nb, int fit) {
             const bool fit_last = c->res_fit_last ? c->res_fit_last == 2 : (uint64_t)res_stream * 10u >= (uint64_t)c->res_max_wgs * 9u;
             const void *fn = resident_fn(p->dev.w_is_mass != 0, ubox, whole, fit_last);
             const uint32_t lanes = GrResShape::LANES, lds = GrResShape::LDS_BYTES;
-            // start handshake (count, verdict) and the waves' progress words back to zero: one small kernel instead of two memsets
-            k_res_prepare<<<dim3((res_stream * 8 + 255) / 256), dim3(256), 0, S>>>(c->res_abort + 1, c->res_progress, res_stream * 8);
-            HIPCHK(c, hipGetLastError());
-            if (c->res_test_no_start) { const uint32_t two = 2u; c->res_test_no_start = 0; HIPCHK(c, hipMemcpyAsync(c->res_abort + 2, &two, sizeof two, hipMemcpyHostToDevice, S)); HIPCHK(c, hipStreamSynchronize(S)); }
+            // (nothing is zeroed for the launch: its handshake words describe themselves, gr_resident.h)
+            st = res_test_no_start(c, ctl.epoch); if (st) return st;
             if (c->profile) EVREC(c, c->pev[0], true, S);
             // An ORDINARY launch: the grid fits the device with one workgroup per CU (resident_wgs checked), other kernels that hold
             // CUs when it starts finish on their own, and the guard above keeps a second resident launch of this process away.
@@ -2351,11 +2435,12 @@ static int segment_begin(gr_rmsd_plan *p, uint32_t s0, uint32_t nb, int fit) {
             const hipError_t le = hipLaunchKernel(fn, dim3(res_stream + n_fin), dim3(lanes), args, lds, S);
             if (le == hipSuccess) {
                 if (c->profile) EVREC(c, c->pev[1], true, S);
-                k_rmsd_close<<<dim3(nb), dim3(64), 0, S>>>(c->fit_partials, res_wgs * GrResShape::WAVES, p->dev.sw, c->state_dev);
-                HIPCHK(c, hipGetLastError());
-                // (the launch's control words follow it on the stream into pinned memory: segment_end reads them after its one synchronisation
-                //  instead of fetching them with a blocking copy of their own -- 15-25 us per call)
-                HIPCHK(c, hipMemcpyAsync(c->res_words_host, c->res_abort, 12 * sizeof(uint32_t), hipMemcpyDeviceToHost, S));
+                c->res_checkin += res_stream + n_fin;
+                // one kernel behind the launch closes the frames' rmsd and hands states and control words to the host through mapped
+                // memory; segment_end polls its sequence word: no copy, no stream synchronisation
+                q.res_fresh = states_unset; q.res_epoch = ctl.epoch;
+                states_unset = false;
+                st = res_close<0>(c, nb, c->fit_partials, res_wgs * GrResShape::WAVES, p->dev.sw, ctl.epoch, q.res_fresh, &q.res_seq); if (st) return st;
                 q.resident = true; q.res_stream = res_stream; q.res_streams = res_streams;
                 q.rmsd_fast = false;                    // (the pass closes its frames with the fit's own sum: nothing to hand back)
                 c->res_last_streams = res_streams;
@@ -2365,6 +2450,7 @@ static int segment_begin(gr_rmsd_plan *p, uint32_t s0, uint32_t nb, int fit) {
                 resident_done(c);
             }
         }
+        if (!q.resident) { st = zero_states(); if (st) return st; }
         for (uint32_t g = 0; g < n_groups && !q.resident; ++g) {
             const uint32_t f0 = g * sb, nf = std::min<uint32_t>(sb, nb - f0), nch = batch_chunks(c, sel, nf), gx = fit_grid(c, nf);
             GrAccPartial *parts = c->acc_partials + (size_t)f0 * GR_MAX_CHUNKS;
@@ -2397,7 +2483,7 @@ static int segment_begin(gr_rmsd_plan *p, uint32_t s0, uint32_t nb, int fit) {
         HIPCHK(c, hipGetLastError());
         if (c->profile) q.n_prof_groups = q.resident ? 0 : n_groups;
     }
-    HIPCHK(c, hipMemcpyAsync(c->state_host, c->state_dev, nb * sizeof(GrFrameState), hipMemcpyDeviceToHost, c->stream));
+    if (!q.resident) HIPCHK(c, hipMemcpyAsync(c->state_host, c->state_dev, nb * sizeof(GrFrameState), hipMemcpyDeviceToHost, c->stream));
     return GR_OK;
 }
 
@@ -2424,7 +2510,9 @@ static int segment_end(gr_rmsd_plan *p, float *rmsd_out, int *status_out, float 
     } else {
         if (!q.has_group) return fail(c, GR_E_INVALID_ARG, "batch state lost");
         const GrSel sel = q.sel;
+        bool res_started = false;
         if (q.small) { const int sw = small_wait(c, q.small_seq); if (sw) return sw; c->state_host[0] = *c->small_state; }
+        else if (q.resident) { const int sw = res_collect(c, q.res_seq, nb, q.res_epoch, &res_started); if (sw) { resident_done(c); return sw; } }
         else HIPCHK(c, hipStreamSynchronize(c->stream));
         std::vector<uint8_t> redo;      // frames of an aborted resident launch that nobody touched: redone on the two-pass path below
         std::vector<uint8_t> torn;      // ... and frames that SOME waves fitted and others did not
@@ -2455,9 +2543,7 @@ static int segment_end(gr_rmsd_plan *p, float *rmsd_out, int *status_out, float 
 #endif
         if (q.resident) {
             resident_done(c);
-            uint32_t words[3] = { 0, 0, 0 };
-            words[0] = c->res_words_host[0]; words[1] = c->res_words_host[1]; words[2] = c->res_words_host[2];   // (copied behind the launch: segment_begin)
-            if (words[2] != 1u) {
+            if (!res_started) {
                 // the launch never started (its workgroups did not all get onto the chip: the device is shared): no frame was
                 // touched -- the segment runs on the two-pass path, and this context sits out the next segments (twice as many after
                 // every miss in a row) before it tries the pass again
@@ -2471,7 +2557,8 @@ static int segment_end(gr_rmsd_plan *p, float *rmsd_out, int *status_out, float 
                 return segment_end(p, rmsd_out, status_out, R_out, final_states);
             }
             c->res_backoff = 0;
-            const uint32_t aborted = words[0];
+            if (q.res_fresh) c->res_lean_segments++;
+            const uint32_t aborted = c->res_words_host[0];
             if (aborted) {
                 // A wait inside the launch ran out of patience (or a test asked for it) and the grid drained.  Every streaming wave left
                 // word of how many frames it had been through (ctl.progress; waves only ever leave between two frames):
@@ -2594,8 +2681,11 @@ static int segment_end(gr_rmsd_plan *p, float *rmsd_out, int *status_out, float 
                 }
             }
             if (c->profile) {
+                // (the kernel behind the second event has answered, so the event has passed; should the runtime not have taken note yet, wait for it)
                 float ms = 0.f;
-                HIPCHK(c, hipEventElapsedTime(&ms, c->pev[0], c->pev[1]));
+                hipError_t ee = hipEventElapsedTime(&ms, c->pev[0], c->pev[1]);
+                if (ee == hipErrorNotReady) { (void)hipGetLastError(); HIPCHK(c, hipEventSynchronize(c->pev[1])); ee = hipEventElapsedTime(&ms, c->pev[0], c->pev[1]); }
+                HIPCHK(c, ee);
                 c->prof_ms[3] += ms; c->prof_launches[3] += 1; c->prof_frames[3] += nb;
             }
         }

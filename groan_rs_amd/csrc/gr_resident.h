@@ -82,6 +82,15 @@
 // agent scope (bypassing the non-coherent caches): a reader can never take a word of an older launch for a new one, nothing has
 // to be cleared between launches, and no store has to be ordered against another -- which keeps "s_waitcnt vmcnt(0)" (a drain
 // of the wave's prefetched rows) out of the streaming loop.
+// The START HANDSHAKE's words are of the same kind, so no kernel zeroes anything before a launch: the check-in count only ever
+// counts up (every workgroup of every launch checks in exactly once, started or not; the host passes the count at which THIS launch
+// is complete, ctl.checkin_target, and all arithmetic on it is modulo 2^32), the verdict is one 64-bit word verdict | epoch << 32,
+// the metronome's origin is written before the verdict and read after it, the clock of the last wave's exit is a maximum over a
+// clock that never runs backwards, the late / waited slot counts run on (the host subtracts what it saw after the launch before)
+// and every streaming wave of a launch that started writes its `progress` word before it leaves.  The epoch is 32 bits: when it
+// wraps the host clears every tagged word and starts again at 1 (res_next_epoch, gr_api.hip).
+// BEHIND the launch one small kernel (k_res_close) adds up the fit sums, hands every frame's closed state and the control words to
+// the host through mapped memory and, last of all, stores the call's sequence number there: the host polls that word.
 // Inside a workgroup (no barrier in the loop): a wave writes its record to LDS, RELEASES it with a workgroup-scope fence
 // restricted to the LDS address space (one s_waitcnt lgkmcnt(0); the unrestricted fence would drain the prefetched rows too)
 // and bumps the slot's LDS counter; the wave that later claims the complete frame ACQUIRES with the same kind of fence before it
@@ -138,13 +147,16 @@ struct GrResShape {
 struct GrResCtl {
     unsigned long long *wgrec;     // [frames][n_stream padded][32] value | epoch << 32
     unsigned long long *rec;       // [frames][16] value | epoch << 32: 0 status, 1..3 shift, 4..12 R (column-major), 13..15 t0 = -R (COM - first atom)
-    uint32_t *abort;               // [12]: 0 abort (0 = fine), 1 workgroups that have started, 2 start verdict (0 open, 1 go, 2 never started);
+    uint32_t *abort;               // [13]: 0 abort (0 = fine; the host clears it after an abort), 1 workgroups that have checked in, ever;
+                                   // 2-3 start verdict | epoch << 32 (1 go, 2 never started; another epoch: open);
                                    // 4-5 the metronome's origin t0 (device clock, written by the workgroup that opens the launch), 6-7 the clock
-                                   // when the last streaming wave left, 8 slots that waves reached late, 9 slots they waited for;
-                                   // 10, 11 shader-clock and device-clock ticks (/ 256) of workgroup 0's walk;
-                                   // words 1 .. 9 are zeroed by the host before every launch
+                                   // when the last streaming wave left (a running maximum), 8 slots that waves reached late, 9 slots they waited
+                                   // for (both running sums); 10, 11 shader-clock and device-clock ticks (/ 256) of workgroup 0's walk;
+                                   // 12 frames k_res_close has exported, ever.  Nothing here is zeroed before a launch.
     uint32_t *progress;            // [n_stream][8]: turns (frames of its stream) each streaming wave had been through when it left
     uint32_t epoch, n_stream, n_fin;   // n_stream = streams x wgs_frame streaming workgroups, then n_fin finalizers
+    uint32_t checkin_target;       // abort[1] when the last workgroup of THIS launch has checked in
+    uint32_t fresh_states;         // every frame passed the host's checks: a finalizer starts from a value-initialised state instead of loading one
     uint32_t wgs_frame, streams;   // workgroups one frame needs; frame streams the launch runs side by side (stream s: frames s, s + streams, ...)
     uint32_t groups_wg;            // 4-atom groups per streaming workgroup: a multiple of 64, 64 .. GR_RES_GROUPS
     uint32_t team_waves;           // waves of a finalizer workgroup that close one frame together: 1, 2, 4 or 8 with 32 x that >= wgs_frame
@@ -160,13 +172,6 @@ struct GrResCtl {
     unsigned long long *dbg;       // [streaming waves][4]: shader-clock ticks spent waiting for records, fits that polled, XCC | SIMD << 8, total ticks
 #endif
 };
-
-// before a launch: the start handshake's two words (count, verdict) and every streaming wave's progress word are zeroed
-__global__ void k_res_prepare(uint32_t *handshake, uint32_t *progress, uint32_t n_progress) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < 11u) handshake[i] = 0u;                                  // (ctl.abort + 1 .. + 11)
-    if (i < n_progress) progress[i] = 0u;
-}
 
 template <typename T> __device__ __forceinline__ T gr_ld_agent(const T *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ float gr_first_f(float v) { return __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint(v))); }
@@ -309,21 +314,30 @@ __global__ __launch_bounds__(GrResShape::LANES) void k_fit_resident(
     {
         __shared__ uint32_t verdict;
         if (tid == 0) {
+            // the verdict word is open while it carries another launch's epoch; the first to decide wins
+            unsigned long long *vw = reinterpret_cast<unsigned long long *>(ctl.abort + 2);
+            const unsigned long long vtag = (unsigned long long)ctl.epoch << 32;
+            auto decide = [&](uint32_t v) {
+                unsigned long long cur = gr_ld_agent(vw);
+                while ((uint32_t)(cur >> 32) != ctl.epoch &&
+                       !__hip_atomic_compare_exchange_strong(vw, &cur, vtag | v, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) { }
+            };
             const uint32_t n = __hip_atomic_fetch_add(ctl.abort + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u;
-            uint32_t zero = 0u;
-            if (n == gridDim.x) {
+            if (n == ctl.checkin_target) {
                 // the workgroup that opens the launch also sets the metronome's origin: visible (release) before the verdict is
                 __hip_atomic_store(reinterpret_cast<unsigned long long *>(ctl.abort + 4), wall_clock64() + ctl.metro_lead, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                (void)__hip_atomic_compare_exchange_strong(ctl.abort + 2, &zero, 1u, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                decide(1u);
             }
-            uint32_t v, polls = 0;
+            unsigned long long vv;
+            uint32_t polls = 0;
             const unsigned long long t0 = wall_clock64();
-            while ((v = gr_ld_agent(ctl.abort + 2)) == 0u) {
-                if (++polls > GR_RES_START_PATIENCE || ((polls & 255u) == 0 && wall_clock64() - t0 > ctl.start_ticks)) { zero = 0u; (void)__hip_atomic_compare_exchange_strong(ctl.abort + 2, &zero, 2u, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+            while ((uint32_t)((vv = gr_ld_agent(vw)) >> 32) != ctl.epoch) {
+                if (++polls > GR_RES_START_PATIENCE || ((polls & 255u) == 0 && wall_clock64() - t0 > ctl.start_ticks)) decide(2u);
                 __builtin_amdgcn_s_sleep(16);
             }
+            const uint32_t v = (uint32_t)vv;
             verdict = v;
             if (v == 1u) { __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent"); metro_t0 = gr_ld_agent(reinterpret_cast<const unsigned long long *>(ctl.abort + 4)); }
         }
@@ -354,7 +368,7 @@ __global__ __launch_bounds__(GrResShape::LANES) void k_fit_resident(
             lb.bcx = bp->bcx; lb.bcy = bp->bcy; lb.bcz = bp->bcz; lb.r_ws = bp->r_ws; lb.ortho = bp->ortho;
             float g0x, g0y, g0z;
             gr_pos_load(frames + (size_t)(first_slot + f) * frame_stride, sel.start, g0x, g0y, g0z);
-            const int pre_status = state[f].status;
+            const int pre_status = ctl.fresh_states ? 0 : state[f].status;
             // The wave's 32 records are 8 KiB in a row, and the wave reads them AS 8 KiB: eight 16-byte loads per lane, each instruction one
             // contiguous KiB (round 5; until then a lane read its own record's words 8 bytes at a time -- 1024 cache lines touched per wave
             // and look, 16 instructions of 64 scattered 8-byte accesses: a look took microseconds and the looks of all finalizers were a
@@ -420,7 +434,8 @@ __global__ __launch_bounds__(GrResShape::LANES) void k_fit_resident(
 #ifdef GR_EXP_TIMELINE
                 if (ctl.tl) ctl.tl[(size_t)f * 8 + 2] = wall_clock64();
 #endif
-                GrFrameState st = state[f];                            // (closed in registers, stored once: results are read back below)
+                GrFrameState st = {};                                  // (closed in registers, stored once: results are read back below)
+                if (ctl.fresh_states) st.err_index = GR_NOIDX; else st = state[f];
 #ifdef GR_EXP_TIMELINE
                 if (ctl.tl) { if (st.status > 1000000) ctl.tl[0] = 0; ctl.tl[(size_t)f * 8 + 3] = wall_clock64(); }
 #endif
@@ -1234,4 +1249,50 @@ __global__ __launch_bounds__(GrResShape::LANES) void k_fit_resident(
         }
     }
 #endif
+}
+
+// BEHIND the resident launch, one wave per frame: the frame's fit sums become its rmsd exactly as k_rmsd_close forms it (MODE 0), and the
+// frame's closed state goes to the host through mapped memory (`out_states`, 22 words in one store instruction).  A frame of a launch
+// that started from fresh states (ctl.fresh_states) whose finalizer never ran -- the launch never started, or was aborted before the
+// frame -- has no state of this launch in memory: it is recorded as GR_ST_ABORTED, here and in `state`, which is how the host
+// knows such a frame from one that was closed.  Every wave counts itself on a device word that only counts up (`done_target`: its value
+// when this launch's last wave has arrived); the last one copies the launch's 12 control words and then, released at system scope,
+// stores the call's sequence number: the host polls that word (res_wait, gr_api.hip) -- the contract of the single-wave kernels (gr_small.h).
+template <int MODE>
+__global__ __launch_bounds__(64) void k_res_close(const double *__restrict__ fit_partials, uint32_t nparts, double sum_w, GrFrameState *state,
+                                                  const unsigned long long *__restrict__ rec, uint32_t epoch, uint32_t fresh_states, uint32_t *ctl_words,
+                                                  uint32_t done_target, GrFrameState *out_states, uint32_t *out_words, uint32_t *out_seq, uint32_t seq) {
+    constexpr uint32_t NW = sizeof(GrFrameState) / 4u, W_RMSD = offsetof(GrFrameState, rmsd) / 4u, W_STATUS = offsetof(GrFrameState, status) / 4u;
+    static_assert(sizeof(GrFrameState) % 4u == 0 && NW <= 64u, "a frame state is exported by one wave, a word per lane");
+    const uint32_t frame = blockIdx.x, lane = threadIdx.x;
+    uint32_t *sw = reinterpret_cast<uint32_t *>(state + frame);
+    uint32_t w = 0u;
+    if (fresh_states && (uint32_t)(gr_ld_agent(rec + (size_t)frame * 16u) >> 32) != epoch) {
+        GrFrameState z = {};
+        z.err_index = GR_NOIDX; z.status = GR_ST_ABORTED;
+        if (lane < NW) { w = reinterpret_cast<const uint32_t *>(&z)[lane]; sw[lane] = w; }
+    } else if (lane < NW) w = sw[lane];
+    const int status = __shfl((int)w, (int)W_STATUS, 64);
+    if (MODE == 0 && status == 0) {
+        // four independent chains per lane: the loads of a lane do not wait for one another
+        double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+        const double *p = fit_partials + (size_t)frame * nparts;
+        uint32_t k = lane;
+        for (; k + 192 < nparts; k += 256) { s0 += p[k]; s1 += p[k + 64]; s2 += p[k + 128]; s3 += p[k + 192]; }
+        for (; k < nparts; k += 64) s0 += p[k];
+        const double s = gr_wave_sum((s0 + s1) + (s2 + s3));
+        float r = 0.0f;
+        if (lane == 0) { r = (float)sqrt(fmax(s, 0.0) / sum_w); state[frame].rmsd = r; }
+        r = __shfl(r, 0, 64);
+        if (lane == W_RMSD) w = __float_as_uint(r);
+    }
+    if (lane < NW) reinterpret_cast<uint32_t *>(out_states + frame)[lane] = w;
+    __threadfence_system();
+    uint32_t n = 0u;
+    if (lane == 0) n = __hip_atomic_fetch_add(ctl_words + 12, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) + 1u;
+    n = (uint32_t)__builtin_amdgcn_readfirstlane((int)n);
+    if (n != done_target) return;
+    if (lane < 12u) out_words[lane] = gr_ld_agent(ctl_words + lane);
+    __threadfence_system();
+    if (lane == 0) __hip_atomic_store(out_seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }

@@ -364,7 +364,7 @@ class System:
             if st != OK:
                 raise DeviceError("set_tuning", self._err(st)[1], st)
 
-    STAT = {"n_cus": 1, "res_max_wgs": 2, "res_launches": 3, "res_handshake_misses": 4, "res_aborts": 5, "res_redone_frames": 6, "res_last_streams": 7, "rmsd_fast_frames": 8, "rmsd_exact_redos": 9, "xtc_device_frames": 10, "small_calls": 11, "small_sync_fallbacks": 12, "res_metro_period_ns": 13, "res_last_turn_ns": 14, "res_late_permille": 15, "res_sclk_mhz": 16, "center_res_launches": 17, "center_res_redone": 18}
+    STAT = {"n_cus": 1, "res_max_wgs": 2, "res_launches": 3, "res_handshake_misses": 4, "res_aborts": 5, "res_redone_frames": 6, "res_last_streams": 7, "rmsd_fast_frames": 8, "rmsd_exact_redos": 9, "xtc_device_frames": 10, "small_calls": 11, "small_sync_fallbacks": 12, "res_metro_period_ns": 13, "res_last_turn_ns": 14, "res_late_permille": 15, "res_sclk_mhz": 16, "center_res_launches": 17, "center_res_redone": 18, "res_lean_segments": 19, "res_sync_fallbacks": 20}
 
     def stat(self, key):
         """gr_ctx_stat: device facts and counters of the batched RMSD path"""

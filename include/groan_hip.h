@@ -356,7 +356,9 @@ int gr_ctx_set_tuning(gr_ctx *ctx, int key, int64_t value);
  *   GR_STAT_RES_LATE_PERMILLE      thousandths of its metronome slots that waves reached more than a quarter period late
  *   GR_STAT_RES_SCLK_MHZ           shader clock that launch ran at (shader-clock ticks over device-clock ticks of its first workgroup's walk)
  *   GR_STAT_CENTER_RES_LAUNCHES    resident atoms_center launches that started (GR_TUNE_CENTER_RESIDENT)
- *   GR_STAT_CENTER_RES_REDONE      frames those launches handed back to the two passes (an atom without position or mass, sums that are not finite, an abort) */
+ *   GR_STAT_CENTER_RES_REDONE      frames those launches handed back to the two passes (an atom without position or mass, sums that are not finite, an abort)
+ *   GR_STAT_RES_LEAN_SEGMENTS      resident launches (RMSD-fit and atoms_center) that started and whose frames had all passed the host's checks: no state was zeroed or uploaded for them
+ *   GR_STAT_RES_SYNC_FALLBACKS     resident launches whose results the host gave up polling for (20 ms) and synchronised the stream instead */
 enum { GR_STAT_N_CUS = 1, GR_STAT_RES_MAX_WGS = 2, GR_STAT_RES_LAUNCHES = 3, GR_STAT_RES_HANDSHAKE_MISSES = 4, GR_STAT_RES_ABORTS = 5, GR_STAT_RES_REDONE_FRAMES = 6, GR_STAT_RES_LAST_STREAMS = 7,
        GR_STAT_RMSD_FAST_FRAMES = 8 /* frames of RMSD-without-fit calls closed by the f32-chain pass (GR_TUNE_RMSD_FAST) */,
        GR_STAT_RMSD_EXACT_REDOS = 9 /* ... and frames that pass handed back to the exact-product pass */,
@@ -364,7 +366,7 @@ enum { GR_STAT_N_CUS = 1, GR_STAT_RES_MAX_WGS = 2, GR_STAT_RES_LAUNCHES = 3, GR_
        GR_STAT_SMALL_CALLS = 11 /* one-frame calls answered by a single-wave dispatch (GR_TUNE_SMALL_CALLS) */,
        GR_STAT_SMALL_SYNC_FALLBACKS = 12 /* ... of which the host gave up polling for the result (20 ms) and synchronised the stream instead */,
        GR_STAT_RES_METRO_PERIOD_NS = 13, GR_STAT_RES_LAST_TURN_NS = 14, GR_STAT_RES_LATE_PERMILLE = 15, GR_STAT_RES_SCLK_MHZ = 16,
-       GR_STAT_CENTER_RES_LAUNCHES = 17, GR_STAT_CENTER_RES_REDONE = 18 };
+       GR_STAT_CENTER_RES_LAUNCHES = 17, GR_STAT_CENTER_RES_REDONE = 18, GR_STAT_RES_LEAN_SEGMENTS = 19, GR_STAT_RES_SYNC_FALLBACKS = 20 };
 int gr_ctx_stat(const gr_ctx *ctx, int key, uint64_t *value);
 
 /* ---------------------------------------------------------------- text front end: gro structures, ndx index groups (host side)
