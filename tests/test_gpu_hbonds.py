@@ -152,8 +152,8 @@ def test_protein_water_gro(G, pep, topo, full):
 
 
 # ---------------------------------------------------------------- seeded systems against the restatement
-def seeded(seed, box, n_don=300, n_other=400, spread=(-0.2, 1.2)):
-    """donors with 1-3 hydrogens at 0.1 nm, acceptor-only heavy atoms; some atoms outside the box.  Positions in lattice
+def seeded(seed, box, n_don=300, n_other=400, spread=(-0.2, 1.2), max_h=3):
+    """donors with 1-max_h hydrogens at 0.1 nm, acceptor-only heavy atoms; some atoms outside the box.  Positions in lattice
     coordinates of `box` (gro box9).  Returns pos, donors, others, hydrogens, bonds"""
     rng = np.random.default_rng(seed)
     L = np.array([[box[0], 0, 0], [box[5], box[1], 0], [box[7], box[8], box[2]]], np.float64)
@@ -162,7 +162,7 @@ def seeded(seed, box, n_don=300, n_other=400, spread=(-0.2, 1.2)):
         d = len(pos); donors.append(d)
         p = rng.uniform(*spread, 3) @ L
         pos.append(p)
-        for _ in range(rng.integers(1, 4)):
+        for _ in range(rng.integers(1, max_h + 1)):
             v = rng.normal(size=3); v *= 0.1 / np.linalg.norm(v)
             hyds.append(len(pos)); bonds.append((d, len(pos))); pos.append(p + v)
     pos[hyds[0]] = pos[donors[0]].copy()                             # a hydrogen sitting on its donor
