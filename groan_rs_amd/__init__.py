@@ -11,6 +11,7 @@ from .system import (AtomContainer, AtomError, AtomIterator, DeviceError, Dimens
 from .traj import (FrameAnalyze, FrameConvert, FrameConvertAnalyze, RMSDConverterAnalyzer, TrajAnalyzer,
                    TrajAnalysisError, TrajConverter, TrajConverterAnalyzer, TrajReader)
 from .hbonds import HBOND_DTYPE, HBondAnalysis, HBondChain, HBondError
+from .gridmap import GridMap, GridMapError, TileGeometry
 from .xtc import XtcError, XtcFile, XtcWriter
 from .trr import TrrFile, TrrWriter
 from .textio import ParseGroError, ParseNdxError, Structure, read_ndx_groups, system_from_gro, system_read_ndx
@@ -21,6 +22,6 @@ from .parallel import AbortedByOtherRank, Comm, ParallelTrajData, Pool, gather_p
 __all__ = [
     "AtomContainer", "AtomError", "AtomIterator", "DeviceError", "Dimension", "GroanError", "GroupError", "RMSDError", "RMSDPlan",
     "SimBoxError", "System", "pinned_array", "pinned_free", "FrameAnalyze", "FrameConvert", "FrameConvertAnalyze", "RMSDConverterAnalyzer",
-    "TrajAnalyzer", "TrajAnalysisError", "HBOND_DTYPE", "HBondAnalysis", "HBondChain", "HBondError", "TrajConverter", "TrajConverterAnalyzer", "TrajReader",
+    "TrajAnalyzer", "TrajAnalysisError", "HBOND_DTYPE", "HBondAnalysis", "HBondChain", "HBondError", "GridMap", "GridMapError", "TileGeometry", "TrajConverter", "TrajConverterAnalyzer", "TrajReader",
     "XtcError", "XtcFile", "XtcWriter", "ParseGroError", "ParseNdxError", "Structure", "read_ndx_groups", "system_from_gro", "system_read_ndx", "Cylinder", "Rectangular", "Shape", "Sphere", "TriangularPrism", "AbortedByOtherRank", "Comm", "Pool", "ParallelTrajData", "gather_per_frame", "interleave", "shard_frames", "traj_iter_map_reduce",
 ]

@@ -17,9 +17,13 @@ c_i32p = C.POINTER(C.c_int)
 # status codes (include/groan_hip.h)
 (OK, E_NO_BOX, E_NOT_ORTHOGONAL, E_ZERO_BOX, E_EMPTY_GROUP, E_INCONSISTENT_GROUP, E_NO_POSITION, E_NO_MASS,
  E_GROUP_NOT_FOUND, E_OUT_OF_RANGE, E_INVALID_ARG, E_GROUP_EXISTS, E_HIP, E_NO_DEVICE, E_UNSUPPORTED_BOX, E_IO, E_FORMAT,
- E_INVALID_NAME, E_EMPTY_CHAIN, E_NONEXISTENT_CHAIN, E_DUPLICATE_PAIR, E_UNUSED_CHAIN, E_INVALID_BOND) = range(23)
+ E_INVALID_NAME, E_EMPTY_CHAIN, E_NONEXISTENT_CHAIN, E_DUPLICATE_PAIR, E_UNUSED_CHAIN, E_INVALID_BOND, E_INVALID_SPAN,
+ E_INVALID_TILE) = range(25)
 
 CENTER_NAIVE, CENTER_ESTIMATE, CENTER_PBC = 0, 1, 2
+GM_COUNT, GM_X, GM_Y, GM_Z = 0, 1, 2, 3
+GM_WRAP, GM_FORCE_GLOBAL = 1, 2
+GM_STAT_LDS_LAUNCHES, GM_STAT_GLOBAL_LAUNCHES, GM_STAT_LDS_BUDGET = 1, 2, 3
 
 # every symbol include/groan_hip.h declares: name -> (restype, argtypes)
 SIGNATURES = {
@@ -133,6 +137,17 @@ SIGNATURES = {
     "gr_make_molecules_whole_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     "gr_make_group_whole": (C.c_int, [C.c_void_p, C.c_uint32, C.c_char_p]),
     "gr_make_group_whole_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_void_p]),
+    "gr_gridmap_len": (C.c_int, [C.c_void_p, C.c_float, c_u64p]),
+    "gr_gridmap_coord2index": (C.c_int64, [C.c_float, C.c_float, C.c_float]),
+    "gr_gridmap_index2coord": (C.c_float, [C.c_float, C.c_float, C.c_uint64]),
+    "gr_gridmap_create": (C.c_void_p, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_i32p]),
+    "gr_gridmap_from_box": (C.c_void_p, [C.c_void_p, C.c_uint32, C.c_void_p, c_i32p]),
+    "gr_gridmap_destroy": (None, [C.c_void_p]),
+    "gr_gridmap_dims": (C.c_int, [C.c_void_p, c_u64p, c_u64p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gr_gridmap_stat": (C.c_int, [C.c_void_p, C.c_int, c_u64p]),
+    "gr_gridmap_clear": (C.c_int, [C.c_void_p]),
+    "gr_gridmap_accumulate_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "gr_gridmap_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gr_group_center_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "gr_group_translate_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_void_p, C.c_void_p]),
     "gr_group_wrap_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_void_p]),

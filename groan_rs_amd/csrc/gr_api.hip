@@ -817,6 +817,8 @@ const char *gr_status_string(int s) try {
     case GR_E_DUPLICATE_PAIR: return "pair of chains requested multiple times";
     case GR_E_UNUSED_CHAIN: return "not all chains are used";
     case GR_E_INVALID_BOND: return "invalid bond";
+    case GR_E_INVALID_SPAN: return "invalid span of the grid map";
+    case GR_E_INVALID_TILE: return "invalid grid tile";
     default: return "unknown status";
     }
 } catch (...) { return nullptr; }
@@ -3842,3 +3844,4 @@ int gr_synth_uniform(gr_ctx *c, uint32_t slot, const float *box9, uint64_t seed)
 
 #include "gr_hbonds.h"   // hydrogen bonds: kernels, plan and C ABI (after the context and its helpers)
 #include "gr_whole.h"    // bond topology, make_molecules_whole / make_group_whole: kernels and C ABI
+#include "gr_gridmap.h"  // GridMap: tile maps accumulated over batches of resident frames: geometry, kernels and C ABI

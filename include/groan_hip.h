@@ -39,6 +39,7 @@ extern "C" {
 typedef struct gr_ctx gr_ctx;
 typedef struct gr_rmsd_plan gr_rmsd_plan;
 typedef struct gr_hbond_plan gr_hbond_plan;
+typedef struct gr_gridmap gr_gridmap;
 typedef struct gr_xtc gr_xtc;
 
 /* status codes; 1..7 map onto the reference's error enums (src/errors.rs) */
@@ -67,7 +68,9 @@ enum {
     GR_E_NONEXISTENT_CHAIN = 19, /* HBondError::NonexistentChain(chain); index = chain          */
     GR_E_DUPLICATE_PAIR = 20,    /* HBondError::PairSpecifiedMultipleTimes; index = ordinal of the repeated pair */
     GR_E_UNUSED_CHAIN = 21,      /* HBondError::UnusedChain                                      */
-    GR_E_INVALID_BOND = 22       /* AtomError::InvalidBond(i, j)          errors.rs:295-296; gr_last_error_counts = (i, j) */
+    GR_E_INVALID_BOND = 22,      /* AtomError::InvalidBond(i, j)          errors.rs:295-296; gr_last_error_counts = (i, j) */
+    GR_E_INVALID_SPAN = 23,      /* GridMapError::InvalidSpan             gridmap.rs:146-150 */
+    GR_E_INVALID_TILE = 24       /* GridMapError::InvalidGridTile         gridmap.rs:152-154 */
 };
 
 /* Dimension (src/structures/dimension.rs:13-23) */
@@ -472,6 +475,60 @@ int gr_make_molecules_whole(gr_ctx *ctx, uint32_t slot);                        
 int gr_make_molecules_whole_batch(gr_ctx *ctx, uint32_t first_slot, uint32_t n_frames, int *status_out);
 int gr_make_group_whole(gr_ctx *ctx, uint32_t slot, const char *group);                          /* modifying.rs:447-475 */
 int gr_make_group_whole_batch(gr_ctx *ctx, uint32_t first_slot, uint32_t n_frames, const char *group, int *status_out);
+
+/* ---------------------------------------------------------------- GridMap: xy tile maps accumulated over resident frames
+ * GridMap (src/structures/gridmap.rs): nx x ny tiles over (span_x, span_y), tile (ix, iy) centred on (span_x[0] + ix * tile_dim[0],
+ * span_y[0] + iy * tile_dim[1]) -- the map really covers span0 - tile / 2 .. span1 + tile / 2.  The reference is a container its
+ * user's trajectory loop fills atom by atom; here the loop runs on the device over a batch of resident frames, and the map holds,
+ * per tile, a COUNT and the SUM of one coordinate of the atoms that fell into it -- what density, height and thickness maps are
+ * made of.  All arithmetic is the reference's, in f32:
+ *   gr_gridmap_len          get_len (gridmap.rs:146-157): span[1] - span[0] < 0 is GR_E_INVALID_SPAN; tile > that difference or
+ *                           tile == 0 is GR_E_INVALID_TILE; else *n = round(diff / tile) + 1.  NaN in the span or the tile and a
+ *                           negative tile are GR_E_INVALID_ARG, and so is a map of more than 2^26 tiles (create / from_box).
+ *   gr_gridmap_coord2index  x2index / y2index (:715-724): round((coord - span0) / tile), half away from zero, converted like Rust's
+ *                           `as isize` (NaN -> 0, +-inf and huge values -> INT64_MAX / INT64_MIN).  A point is INSIDE the map when
+ *                           0 <= ix < nx and 0 <= iy < ny.
+ *   gr_gridmap_index2coord  index2x / index2y (:729-738): (float)index * tile + span0, two roundings (never an fma), the same bits
+ *                           on the host and on the device.
+ *   gr_gridmap_create       GridMap::new (:122-140); gr_gridmap_from_box: GridMap::from_box (:164-173), spans (0, box.x), (0, box.y)
+ *                           of the slot's box: GR_E_NO_BOX without one, GR_E_NOT_ORTHOGONAL for a non-orthogonal box in EVERY mode
+ *                           (the tile plane of a skewed cell is not defined).  The map keeps a pointer to the context: destroy it first.
+ *   gr_gridmap_accumulate_batch  for every frame f of the n_frames slots from first_slot that passes its checks, and every atom of
+ *                           `group`: (x, y, z) = its position -- with GR_GM_WRAP the position gr_group_wrap would give it (the frame
+ *                           is not modified; needs the frame's box: GR_E_NO_BOX / GR_E_ZERO_BOX / GR_E_NOT_ORTHOGONAL in strict mode
+ *                           / GR_E_UNSUPPORTED_BOX; without GR_GM_WRAP no box is needed, as in the reference); ix, iy as above; an
+ *                           atom that is not inside adds 1 to n_outside[f] and nothing else; otherwise count[ix, iy] += 1 and, for
+ *                           value = GR_GM_X / _Y / _Z, sum_q[ix, iy] += (int64) rint((double) v * 2^20) with v = coordinate -
+ *                           offset[f] in f32 (offset NULL: 0).  An atom whose v is not finite or has |v| >= 2^31 counts as outside.
+ *                           The sums are 64-bit INTEGERS in units of 2^-20 nm (far below xtc precision): integer adds commute, so a
+ *                           map is the same bit for bit whatever the order of the adds -- on every path, across calls and across
+ *                           runs.  Capacity of a tile: 2^32 contributions of 2048 nm.
+ *                           Errors: GR_E_GROUP_NOT_FOUND, GR_E_EMPTY_GROUP; per frame (batch rules below: status_out[f], the return
+ *                           value is the first failed frame's status, message and gr_last_error_index) the box statuses above and
+ *                           GR_E_NO_POSITION with index = the first atom of the group, in group order, without position.  A failed
+ *                           frame contributes NOTHING and has n_outside[f] = 0 (the reference's loop would have binned the atoms in
+ *                           front of the failing one).  Any number of frames, as gr_group_center_batch.
+ *                           A map whose privatised copy fits 64 KiB of LDS (12 bytes per tile, 4 when only counting) is accumulated
+ *                           per workgroup in LDS over many frames and flushed once; larger maps, and GR_GM_FORCE_GLOBAL, add to
+ *                           global memory directly (gr_gridmap_stat counts the launches of either kind).  Same bits either way.
+ *   gr_gridmap_read         count, sum_q, mean = (float)((double) sum_q * 2^-20 / (double) count) (NaN where count == 0), each
+ *                           [nx * ny], row-major with x the outer index; any may be NULL.  gr_gridmap_clear zeroes the map. */
+enum { GR_GM_COUNT = 0, GR_GM_X = 1, GR_GM_Y = 2, GR_GM_Z = 3 };          /* what is summed per tile besides the count */
+enum { GR_GM_WRAP = 1, GR_GM_FORCE_GLOBAL = 2 };                           /* flags */
+enum { GR_GM_STAT_LDS_LAUNCHES = 1, GR_GM_STAT_GLOBAL_LAUNCHES = 2, GR_GM_STAT_LDS_BUDGET = 3 /* bytes */ };
+int gr_gridmap_len(const float span[2], float tile, uint64_t *n);
+int64_t gr_gridmap_coord2index(float span0, float tile, float coord);
+float gr_gridmap_index2coord(float span0, float tile, uint64_t index);
+gr_gridmap *gr_gridmap_create(gr_ctx *ctx, const float span_x[2], const float span_y[2], const float tile_dim[2], int *status);
+gr_gridmap *gr_gridmap_from_box(gr_ctx *ctx, uint32_t slot, const float tile_dim[2], int *status);
+void gr_gridmap_destroy(gr_gridmap *map);
+int gr_gridmap_dims(const gr_gridmap *map, uint64_t *nx, uint64_t *ny, float span_x[2], float span_y[2], float tile_dim[2]);
+int gr_gridmap_stat(const gr_gridmap *map, int key, uint64_t *value);
+int gr_gridmap_clear(gr_gridmap *map);
+int gr_gridmap_accumulate_batch(gr_gridmap *map, uint32_t first_slot, uint32_t n_frames, const char *group, int value,
+                                const float *offset /* [n_frames] or NULL */, int flags,
+                                uint64_t *n_outside /* [n_frames] or NULL */, int *status_out /* [n_frames] or NULL */);
+int gr_gridmap_read(gr_gridmap *map, uint64_t *count, int64_t *sum_q, float *mean);
 
 /* ---------------------------------------------------------------- per-frame analyses over a batch of slots
  * The calls above for `n_frames` consecutive slots in ONE set of launches and one read-back (a trajectory loop of

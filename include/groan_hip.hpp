@@ -653,4 +653,90 @@ class HBondPlan {
     uint64_t cap_ = 0;
 };
 
+// ---- GridMap (src/structures/gridmap.rs): an xy tile map accumulated over batches of resident frames
+enum class GridValue : int { Count = GR_GM_COUNT, X = GR_GM_X, Y = GR_GM_Y, Z = GR_GM_Z };
+
+class GridMap {
+  public:
+    GridMap(System &system, std::pair<float, float> span_x, std::pair<float, float> span_y, std::pair<float, float> tile_dim) : ctx_(system.raw()) {
+        const float sx[2] = { span_x.first, span_x.second }, sy[2] = { span_y.first, span_y.second }, td[2] = { tile_dim.first, tile_dim.second };
+        int st = 0;
+        map_ = gr_gridmap_create(ctx_, sx, sy, td, &st);
+        if (!map_) raise(st);
+        dims();
+    }
+    // GridMap::from_box: spans (0, box.x), (0, box.y) of the slot's box; orthogonal boxes only
+    static GridMap from_box(System &system, std::pair<float, float> tile_dim, uint32_t slot = 0) {
+        GridMap m(system.raw());
+        const float td[2] = { tile_dim.first, tile_dim.second };
+        int st = 0;
+        m.map_ = gr_gridmap_from_box(m.ctx_, slot, td, &st);
+        if (!m.map_) m.raise(st);
+        m.dims();
+        return m;
+    }
+    ~GridMap() { if (map_) gr_gridmap_destroy(map_); }
+    GridMap(const GridMap &) = delete;
+    GridMap &operator=(const GridMap &) = delete;
+    GridMap(GridMap &&o) noexcept : ctx_(o.ctx_), map_(o.map_), nx_(o.nx_), ny_(o.ny_), span_x_(o.span_x_), span_y_(o.span_y_), tile_(o.tile_) { o.map_ = nullptr; }
+
+    uint64_t n_tiles_x() const { return nx_; }
+    uint64_t n_tiles_y() const { return ny_; }
+    uint64_t n_tiles() const { return nx_ * ny_; }
+    bool is_inside(float x, float y) const {
+        const int64_t ix = gr_gridmap_coord2index(span_x_.first, tile_.first, x), iy = gr_gridmap_coord2index(span_y_.first, tile_.second, y);
+        return ix >= 0 && (uint64_t)ix < nx_ && iy >= 0 && (uint64_t)iy < ny_;
+    }
+    // the tile's coordinates; false outside the map
+    bool get_tile(float x, float y, float &tx, float &ty) const {
+        if (!is_inside(x, y)) return false;
+        tx = gr_gridmap_index2coord(span_x_.first, tile_.first, (uint64_t)gr_gridmap_coord2index(span_x_.first, tile_.first, x));
+        ty = gr_gridmap_index2coord(span_y_.first, tile_.second, (uint64_t)gr_gridmap_coord2index(span_y_.first, tile_.second, y));
+        return true;
+    }
+    // bin the atoms of `group` of n_frames resident slots; -> atoms outside the map per frame.  A failed frame throws the first
+    // failure unless `status` is given, which then receives every frame's status
+    std::vector<uint64_t> accumulate(const std::string &group, uint32_t first_slot, uint32_t n_frames, GridValue value = GridValue::Count,
+                                     const std::vector<float> *offset = nullptr, bool wrap = false, std::vector<int> *status = nullptr) {
+        if (offset && offset->size() != n_frames) throw std::invalid_argument("GridMap::accumulate | one offset per frame");
+        std::vector<uint64_t> outside(n_frames);
+        std::vector<int> st(n_frames);
+        const int r = gr_gridmap_accumulate_batch(map_, first_slot, n_frames, group.c_str(), (int)value, offset ? offset->data() : nullptr, wrap ? GR_GM_WRAP : 0,
+                                                  outside.data(), st.data());
+        if (status) *status = st;
+        else if (r != GR_OK) raise(r);
+        return outside;
+    }
+    void clear() { const int st = gr_gridmap_clear(map_); if (st != GR_OK) raise(st); }
+    std::vector<uint64_t> counts() { std::vector<uint64_t> v(n_tiles()); read(v.data(), nullptr, nullptr); return v; }      // row-major, x outer
+    std::vector<int64_t> sums_q() { std::vector<int64_t> v(n_tiles()); read(nullptr, v.data(), nullptr); return v; }        // units of 2^-20 nm
+    std::vector<float> mean() { std::vector<float> v(n_tiles()); read(nullptr, nullptr, v.data()); return v; }              // NaN where nothing was counted
+    gr_gridmap *raw() const { return map_; }
+
+  private:
+    explicit GridMap(gr_ctx *ctx) : ctx_(ctx) {}
+    void dims() {
+        float sx[2], sy[2], td[2];
+        gr_gridmap_dims(map_, &nx_, &ny_, sx, sy, td);
+        span_x_ = { sx[0], sx[1] }; span_y_ = { sy[0], sy[1] }; tile_ = { td[0], td[1] };
+    }
+    void read(uint64_t *c, int64_t *s, float *m) { const int st = gr_gridmap_read(map_, c, s, m); if (st != GR_OK) raise(st); }
+    [[noreturn]] void raise(int st) const {
+        const uint64_t idx = gr_last_error_index(ctx_);
+        switch (st) {
+        case GR_E_INVALID_SPAN: throw Error("GridMapError", "InvalidSpan", st);
+        case GR_E_INVALID_TILE: throw Error("GridMapError", "InvalidGridTile", st);
+        case GR_E_GROUP_NOT_FOUND: throw Error("GroupError", "NotFound", st);
+        case GR_E_EMPTY_GROUP: throw Error("GroupError", "EmptyGroup", st);
+        case GR_E_NO_POSITION: throw Error("GroupError", "InvalidPosition", st, idx);
+        case GR_E_NO_BOX: case GR_E_NOT_ORTHOGONAL: case GR_E_ZERO_BOX: throw Error("GridMapError", "InvalidSimBox(" + simbox_variant(st) + ")", st);
+        default: throw Error("DeviceError", std::string(gr_status_string(st)) + ": " + gr_last_error(ctx_), st);
+        }
+    }
+    gr_ctx *ctx_ = nullptr;
+    gr_gridmap *map_ = nullptr;
+    uint64_t nx_ = 0, ny_ = 0;
+    std::pair<float, float> span_x_{ 0.f, 0.f }, span_y_{ 0.f, 0.f }, tile_{ 0.f, 0.f };
+};
+
 }  // namespace groan

@@ -33,8 +33,17 @@ pub const GR_E_NONEXISTENT_CHAIN: c_int = 19;
 pub const GR_E_DUPLICATE_PAIR: c_int = 20;
 pub const GR_E_UNUSED_CHAIN: c_int = 21;
 pub const GR_E_INVALID_BOND: c_int = 22;
+pub const GR_E_INVALID_SPAN: c_int = 23;
+pub const GR_E_INVALID_TILE: c_int = 24;
+pub const GR_GM_COUNT: c_int = 0;
+pub const GR_GM_X: c_int = 1;
+pub const GR_GM_Y: c_int = 2;
+pub const GR_GM_Z: c_int = 3;
+pub const GR_GM_WRAP: c_int = 1;
+pub const GR_GM_FORCE_GLOBAL: c_int = 2;
 
 #[repr(C)] pub struct gr_hbond_plan { _private: [u8; 0] }
+#[repr(C)] pub struct gr_gridmap { _private: [u8; 0] }
 #[repr(C)] pub struct gr_pool { _private: [u8; 0] }
 #[repr(C)] pub struct gr_comm { _private: [u8; 0] }
 /// `body(ctx, worker, frame, user, result)` of gr_pool_map: non-zero return = the frame's error (the first one wins)
@@ -132,6 +141,19 @@ extern "C" {
     pub fn gr_make_molecules_whole_batch(ctx: *mut gr_ctx, first_slot: u32, n_frames: u32, status: *mut c_int) -> c_int;
     pub fn gr_make_group_whole(ctx: *mut gr_ctx, slot: u32, group: *const c_char) -> c_int;
     pub fn gr_make_group_whole_batch(ctx: *mut gr_ctx, first_slot: u32, n_frames: u32, group: *const c_char, status: *mut c_int) -> c_int;
+    // GridMap (src/structures/gridmap.rs) accumulated over batches of resident frames: count and integer coordinate sum per tile
+    pub fn gr_gridmap_len(span: *const c_float, tile: c_float, n: *mut u64) -> c_int;
+    pub fn gr_gridmap_coord2index(span0: c_float, tile: c_float, coord: c_float) -> i64;
+    pub fn gr_gridmap_index2coord(span0: c_float, tile: c_float, index: u64) -> c_float;
+    pub fn gr_gridmap_create(ctx: *mut gr_ctx, span_x: *const c_float, span_y: *const c_float, tile_dim: *const c_float, status: *mut c_int) -> *mut gr_gridmap;
+    pub fn gr_gridmap_from_box(ctx: *mut gr_ctx, slot: u32, tile_dim: *const c_float, status: *mut c_int) -> *mut gr_gridmap;
+    pub fn gr_gridmap_destroy(map: *mut gr_gridmap);
+    pub fn gr_gridmap_dims(map: *const gr_gridmap, nx: *mut u64, ny: *mut u64, span_x: *mut c_float, span_y: *mut c_float, tile_dim: *mut c_float) -> c_int;
+    pub fn gr_gridmap_stat(map: *const gr_gridmap, key: c_int, value: *mut u64) -> c_int;
+    pub fn gr_gridmap_clear(map: *mut gr_gridmap) -> c_int;
+    pub fn gr_gridmap_accumulate_batch(map: *mut gr_gridmap, first_slot: u32, n_frames: u32, group: *const c_char, value: c_int, offset: *const c_float,
+                                       flags: c_int, n_outside: *mut u64, status_out: *mut c_int) -> c_int;
+    pub fn gr_gridmap_read(map: *mut gr_gridmap, count: *mut u64, sum_q: *mut i64, mean: *mut c_float) -> c_int;
     pub fn gr_ctx_set_tuning(ctx: *mut gr_ctx, key: c_int, value: i64) -> c_int;   // GR_TUNE_* (include/groan_hip.h)
     pub fn gr_host_alloc(bytes: usize) -> *mut c_void;                              // pinned memory: asynchronous gr_frame_upload
     pub fn gr_host_free(p: *mut c_void);
