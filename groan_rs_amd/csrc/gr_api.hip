@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/groan_hip.h"
+#include "gr_batch.h"
 #include "gr_container.h"
 #include "gr_kernels.h"
 #include "gr_hot.h"
@@ -33,7 +34,6 @@
 #include <system_error>
 #include <chrono>
 
-#define GR_MAX_BATCH 1024    // frames per batched call segment (workspace is sized for this; 82 MB of partial records)
 #define GR_MAX_CHUNKS 256    // workgroups per frame in the reduction kernels
 
 namespace {
@@ -498,6 +498,13 @@ const Group *find_group(const gr_ctx *c, const char *name) {
     if (!name) return nullptr;
     auto it = c->groups.find(name);
     return it == c->groups.end() ? nullptr : &it->second;
+}
+// the group an entry point works on: nullptr with the call's error in `st` where it does not exist -- or, for `non_empty`, has no atoms
+const Group *need_group(gr_ctx *c, const char *name, int &st, bool non_empty = false) {
+    const Group *g = find_group(c, name);
+    if (g && !(non_empty && g->n == 0)) return g;
+    st = g ? fail(c, GR_E_EMPTY_GROUP, name) : fail(c, GR_E_GROUP_NOT_FOUND, name ? name : "(null)");
+    return nullptr;
 }
 
 // simbox_check (simbox.rs:230-236) for one slot
@@ -1177,9 +1184,7 @@ static int center_core(gr_ctx *c, uint32_t slot, const Group &g, int kind, int w
 int gr_group_center(gr_ctx *c, uint32_t slot, const char *group, int kind, int weighted, float out[3]) try {
     int st = slot_check(c, slot); if (st) return st;
     (void)hipSetDevice(c->device);
-    const Group *g = find_group(c, group);
-    if (!g) return fail(c, GR_E_GROUP_NOT_FOUND, group ? group : "(null)");
-    if (g->n == 0) return fail(c, GR_E_EMPTY_GROUP, group);               // analysis.rs:52-55
+    const Group *g = need_group(c, group, st, true); if (!g) return st;               // analysis.rs:52-55
     if (kind != GR_CENTER_NAIVE && kind != GR_CENTER_ESTIMATE && kind != GR_CENTER_PBC) return fail(c, GR_E_INVALID_ARG, "unknown centre kind");
     if (kind != GR_CENTER_NAIVE) { st = box_check(c, slot); if (st) return st; }
     return center_core(c, slot, *g, kind, weighted, out);
@@ -1218,7 +1223,8 @@ int gr_group_distance(gr_ctx *c, uint32_t slot, const char *g1, const char *g2, 
     return GR_OK;
 } catch (...) { return gr_abi_guard(); }
 
-static void batch_prechecks(gr_ctx *c, uint32_t s0, uint32_t nb, bool need_box, std::vector<int> &pre, std::vector<std::string> &msg);
+// the host check of a batched call's frames (grb::Prechecks): simbox_check where the call needs a box, else none
+static auto box_checks(gr_ctx *c, bool need_box) { return [=](uint32_t slot) { return need_box ? box_check(c, slot) : (int)GR_OK; }; }
 // pair distances of `nb` consecutive slots in one launch; matrices `out_stride` floats apart; -> bad_host[4 f + 0 / 1]
 static int pairdist_launch(gr_ctx *c, uint32_t s0, uint32_t nb, const GrSel &s1, const GrSel &s2, int dim, float *out_dev, size_t out_stride, const GrPdRed *red = nullptr) {
     SlotUse use(c, s0, nb);
@@ -1285,39 +1291,30 @@ int gr_group_all_distances_batch_device(gr_ctx *c, uint32_t first_slot, uint32_t
                                         float **out_dev, uint64_t *n1, uint64_t *n2, int *status_out) try {
     int st = slot_check(c, first_slot, n_frames); if (st) return st;
     (void)hipSetDevice(c->device);
-    const Group *a = find_group(c, g1); if (!a) return fail(c, GR_E_GROUP_NOT_FOUND, g1 ? g1 : "(null)");
-    const Group *b = find_group(c, g2); if (!b) return fail(c, GR_E_GROUP_NOT_FOUND, g2 ? g2 : "(null)");
+    const Group *a = need_group(c, g1, st); if (!a) return st;
+    const Group *b = need_group(c, g2, st); if (!b) return st;
     if (dim < 0 || dim > 7) return fail(c, GR_E_INVALID_ARG, "bad dimension");
     const size_t per = (size_t)a->n * b->n;
     st = pairdist_reserve(c, per * n_frames); if (st) return st;
     const GrSel s1 = make_sel(*a), s2 = make_sel(*b);
-    int first_err = GR_OK; std::string first_msg; uint64_t first_idx = 0;
-    for (uint32_t b0 = 0; b0 < n_frames; b0 += GR_MAX_BATCH) {
-        const uint32_t nb = std::min<uint32_t>(GR_MAX_BATCH, n_frames - b0), s0 = first_slot + b0;
-        std::vector<int> pre; std::vector<std::string> msg;
-        batch_prechecks(c, s0, nb, true, pre, msg);
+    grb::FirstError<gr_ctx> fe;
+    for (const auto [b0, nb, s0] : grb::Segments{ first_slot, n_frames }) {
+        const grb::Prechecks pre(c, { b0, nb, s0 }, box_checks(c, true));
         st = pairdist_launch(c, s0, nb, s1, s2, dim, c->pd_out + (size_t)b0 * per, per); if (st) return st;
-        for (uint32_t f = 0; f < nb; ++f) {
-            int s = pre[f];
-            if (s != GR_OK) c->err = msg[f];
-            else s = pairdist_status(c, f, s1);
-            if (s != GR_OK && first_err == GR_OK) { first_err = s; first_msg = c->err; first_idx = c->err_index; }
-            if (status_out) status_out[b0 + f] = s;
-        }
+        for (uint32_t f = 0; f < nb; ++f) grb::close_frame(c, fe, pre, f, status_out, [&] { return pairdist_status(c, f, s1); });
     }
     if (out_dev) *out_dev = c->pd_out;
     if (n1) *n1 = a->n;
     if (n2) *n2 = b->n;
-    if (first_err != GR_OK) { c->err = first_msg; c->err_index = first_idx; }
-    return first_err;
+    return fe.finish(c);
 } catch (...) { return gr_abi_guard(); }
 
 int gr_group_all_distances_device(gr_ctx *c, uint32_t slot, const char *g1, const char *g2, int dim,
                                   float **out_dev, uint64_t *n1, uint64_t *n2) try {
     int st = slot_check(c, slot); if (st) return st;
     (void)hipSetDevice(c->device);
-    const Group *a = find_group(c, g1); if (!a) return fail(c, GR_E_GROUP_NOT_FOUND, g1 ? g1 : "(null)");
-    const Group *b = find_group(c, g2); if (!b) return fail(c, GR_E_GROUP_NOT_FOUND, g2 ? g2 : "(null)");
+    const Group *a = need_group(c, g1, st); if (!a) return st;
+    const Group *b = need_group(c, g2, st); if (!b) return st;
     st = box_check(c, slot); if (st) return st;
     if (dim < 0 || dim > 7) return fail(c, GR_E_INVALID_ARG, "bad dimension");
     st = pairdist_reserve(c, (size_t)a->n * b->n); if (st) return st;
@@ -1355,8 +1352,8 @@ int gr_group_all_distances_reduce_batch(gr_ctx *c, uint32_t first_slot, uint32_t
                                         float param, uint32_t nbins, void *out, size_t out_capacity_bytes, int *status_out) try {
     int st = slot_check(c, first_slot, n_frames); if (st) return st;
     (void)hipSetDevice(c->device);
-    const Group *a = find_group(c, g1); if (!a) return fail(c, GR_E_GROUP_NOT_FOUND, g1 ? g1 : "(null)");
-    const Group *b = find_group(c, g2); if (!b) return fail(c, GR_E_GROUP_NOT_FOUND, g2 ? g2 : "(null)");
+    const Group *a = need_group(c, g1, st); if (!a) return st;
+    const Group *b = need_group(c, g2, st); if (!b) return st;
     if (dim < 0 || dim > 7) return fail(c, GR_E_INVALID_ARG, "bad dimension");
     if (op < GR_PD_MIN || op > GR_PD_HIST) return fail(c, GR_E_INVALID_ARG, "unknown reduction");
     if (op == GR_PD_HIST && (per_row || nbins == 0 || nbins > GR_PDR_MAX_BINS || !(param > 0.0f))) return fail(c, GR_E_INVALID_ARG, "histogram: 1 .. 4096 bins over (0, rmax), never per row");
@@ -1372,16 +1369,14 @@ int gr_group_all_distances_reduce_batch(gr_ctx *c, uint32_t first_slot, uint32_t
     const bool acc64 = op == GR_PD_HIST || (op == GR_PD_COUNT_BELOW && !per_row);
     const size_t word_bytes = acc64 ? sizeof(unsigned long long) : sizeof(uint32_t);
     const GrSel s1 = make_sel(*a), s2 = make_sel(*b);
-    int first_err = GR_OK; std::string first_msg; uint64_t first_idx = 0;
+    grb::FirstError<gr_ctx> fe;
     std::vector<uint32_t> host;
     std::vector<unsigned long long> host64;
-    for (uint32_t b0 = 0; b0 < n_frames; b0 += GR_MAX_BATCH) {
-        const uint32_t nb = std::min<uint32_t>(GR_MAX_BATCH, n_frames - b0), s0 = first_slot + b0;
+    for (const auto [b0, nb, s0] : grb::Segments{ first_slot, n_frames }) {
         st = pairdist_reserve(c, ((size_t)nb * words * (word_bytes / sizeof(float)) + 1) & ~(size_t)1); if (st) return st;
         uint32_t *acc = reinterpret_cast<uint32_t *>(c->pd_out);
         HIPCHK(c, hipMemsetAsync(acc, op == GR_PD_MIN ? 0xFF : 0x00, (size_t)nb * words * word_bytes, c->stream));
-        std::vector<int> pre; std::vector<std::string> msg;
-        batch_prechecks(c, s0, nb, true, pre, msg);
+        const grb::Prechecks pre(c, { b0, nb, s0 }, box_checks(c, true));
         // per row of a group of some size: the groups change places and every lane keeps the values of its own four atoms (k_pairdist,
         // "transposed"); a handful of rows against many columns stays as it is (the lanes are the columns)
         const bool transposed = per_row && a->n >= 512;
@@ -1393,11 +1388,7 @@ int gr_group_all_distances_reduce_batch(gr_ctx *c, uint32_t first_slot, uint32_t
         else { host.resize((size_t)nb * words); HIPCHK(c, hipMemcpyAsync(host.data(), acc, host.size() * word_bytes, hipMemcpyDeviceToHost, c->stream)); }
         HIPCHK(c, hipStreamSynchronize(c->stream));
         for (uint32_t f = 0; f < nb; ++f) {
-            int s = pre[f];
-            if (s != GR_OK) c->err = msg[f];
-            else s = pairdist_status(c, f, s1);
-            if (s != GR_OK && first_err == GR_OK) { first_err = s; first_msg = c->err; first_idx = c->err_index; }
-            if (status_out) status_out[b0 + f] = s;
+            grb::close_frame(c, fe, pre, f, status_out, [&] { return pairdist_status(c, f, s1); });
             if (wide) {
                 uint64_t *o = static_cast<uint64_t *>(out) + (size_t)(b0 + f) * len;
                 if (acc64) {
@@ -1416,8 +1407,7 @@ int gr_group_all_distances_reduce_batch(gr_ctx *c, uint32_t first_slot, uint32_t
             }
         }
     }
-    if (first_err != GR_OK) { c->err = first_msg; c->err_index = first_idx; }
-    return first_err;
+    return fe.finish(c);
 } catch (...) { return gr_abi_guard(); }
 int gr_group_all_distances_reduce(gr_ctx *c, uint32_t slot, const char *g1, const char *g2, int dim, int op, int per_row, float param, uint32_t nbins,
                                   void *out, size_t out_capacity_bytes) try {
@@ -1571,8 +1561,7 @@ int gr_group_create_from_geometries(gr_ctx *c, uint32_t slot, const char *name, 
     (void)hipSetDevice(c->device);
     if (!name_is_valid(name)) return fail(c, GR_E_INVALID_NAME, name ? name : "(null)");                 // groups.rs:100-102
     st = geometry_box_check(c, slot); if (st) return st;
-    const Group *g = find_group(c, source);
-    if (!g) return fail(c, GR_E_GROUP_NOT_FOUND, source ? source : "(null)");                               // InvalidQuery(GroupNotFound)
+    const Group *g = need_group(c, source, st); if (!g) return st;                                                          // InvalidQuery(GroupNotFound)
     std::vector<uint64_t> picked;
     st = geometry_filter(c, slot, *g, shapes, ns, naive, picked); if (st) return st;
     return install_group(c, name, grc::from_indices(picked, c->n));
@@ -1623,9 +1612,7 @@ int gr_group_wrap(gr_ctx *c, uint32_t slot, const char *group) try {
 int gr_atoms_center(gr_ctx *c, uint32_t slot, const char *ref_group, int dim, int weighted) try {
     int st = slot_check(c, slot); if (st) return st;
     (void)hipSetDevice(c->device);
-    const Group *g = find_group(c, ref_group);
-    if (!g) return fail(c, GR_E_GROUP_NOT_FOUND, ref_group ? ref_group : "(null)");
-    if (g->n == 0) return fail(c, GR_E_EMPTY_GROUP, ref_group);
+    const Group *g = need_group(c, ref_group, st, true); if (!g) return st;
     st = box_check(c, slot); if (st) return st;
     if (dim < 0 || dim > 7) return fail(c, GR_E_INVALID_ARG, "bad dimension");
     static const int mask[8] = { 0, 1, 2, 4, 3, 5, 6, 7 };
@@ -1722,8 +1709,8 @@ int gr_group_pairs_within(gr_ctx *c, uint32_t slot, const char *g1, const char *
                           uint32_t *i_out, uint32_t *j_out, float *d_out, uint64_t *n_pairs) try {
     int st = slot_check(c, slot); if (st) return st;
     (void)hipSetDevice(c->device);
-    const Group *a = find_group(c, g1); if (!a) return fail(c, GR_E_GROUP_NOT_FOUND, g1 ? g1 : "(null)");
-    const Group *b = find_group(c, g2); if (!b) return fail(c, GR_E_GROUP_NOT_FOUND, g2 ? g2 : "(null)");
+    const Group *a = need_group(c, g1, st); if (!a) return st;
+    const Group *b = need_group(c, g2, st); if (!b) return st;
     if (!(cutoff > 0.0f)) return fail(c, GR_E_INVALID_ARG, "cell size (cut-off) must be positive");              // cellgrid.rs:323-325
     if (c->box_status[slot] == GR_E_NO_BOX) return fail(c, GR_E_NO_BOX, "simulation box does not exist");            // check_box :411-430
     if (c->box_status[slot] != GR_OK) return fail(c, c->box_status[slot], "invalid simulation box");
@@ -1795,41 +1782,25 @@ int gr_group_pairs_within(gr_ctx *c, uint32_t slot, const char *g1, const char *
 } catch (...) { return gr_abi_guard(); }
 
 /* ------------------------------------------------------------ the same per-frame calls over a batch of slots */
-// host checks of one batch in the reference's order; pre[f] = GR_OK or the frame's error (messages kept for the first)
-static void batch_prechecks(gr_ctx *c, uint32_t s0, uint32_t nb, bool need_box, std::vector<int> &pre, std::vector<std::string> &msg) {
-    pre.assign(nb, GR_OK); msg.assign(nb, std::string());
-    for (uint32_t f = 0; f < nb; ++f) {
-        if (!need_box) continue;
-        const int s = box_check(c, s0 + f);
-        pre[f] = s;
-        if (s != GR_OK) msg[f] = c->err;
-    }
-}
 // the frames' states of a batched call start from the host-side checks: zeroed by a kernel when every frame passed them (the usual
 // case), copied out of pinned memory otherwise -- that copy costs ~30 us of host time before the call's first kernel can be queued
-static int states_from_prechecks(gr_ctx *c, uint32_t nb, const std::vector<int> &pre) {
-    bool all_ok = true;
-    for (uint32_t f = 0; f < nb; ++f) all_ok = all_ok && pre[f] == GR_OK;
-    if (all_ok) return state_reset(c, nb);
-    for (uint32_t f = 0; f < nb; ++f) { GrFrameState z = {}; z.err_index = GR_NOIDX; z.status = pre[f]; c->state_host[f] = z; }
-    HIPCHK(c, hipMemcpyAsync(c->state_dev, c->state_host, nb * sizeof(GrFrameState), hipMemcpyHostToDevice, c->stream));
+static int states_from_prechecks(gr_ctx *c, const grb::PreView &pre) {
+    if (pre.all_ok) return state_reset(c, pre.n);
+    for (uint32_t f = 0; f < pre.n; ++f) { GrFrameState z = {}; z.err_index = GR_NOIDX; z.status = pre.pre[f]; c->state_host[f] = z; }
+    HIPCHK(c, hipMemcpyAsync(c->state_dev, c->state_host, pre.n * sizeof(GrFrameState), hipMemcpyHostToDevice, c->stream));
     return GR_OK;
 }
 int gr_group_center_batch(gr_ctx *c, uint32_t first_slot, uint32_t n_frames, const char *group, int kind, int weighted, float *out, int *status_out) try {
     int st = slot_check(c, first_slot, n_frames); if (st) return st;
     (void)hipSetDevice(c->device);
-    const Group *g = find_group(c, group);
-    if (!g) return fail(c, GR_E_GROUP_NOT_FOUND, group ? group : "(null)");
-    if (g->n == 0) return fail(c, GR_E_EMPTY_GROUP, group);
+    const Group *g = need_group(c, group, st, true); if (!g) return st;
     if (kind != GR_CENTER_NAIVE && kind != GR_CENTER_ESTIMATE && kind != GR_CENTER_PBC) return fail(c, GR_E_INVALID_ARG, "unknown centre kind");
     const GrSel sel = make_sel(*g);
-    int first_err = GR_OK; std::string first_msg; uint64_t first_idx = 0;
-    for (uint32_t b0 = 0; b0 < n_frames; b0 += GR_MAX_BATCH) {
-        const uint32_t nb = std::min<uint32_t>(GR_MAX_BATCH, n_frames - b0), s0 = first_slot + b0;
-        std::vector<int> pre; std::vector<std::string> msg;
-        batch_prechecks(c, s0, nb, kind != GR_CENTER_NAIVE, pre, msg);
+    grb::FirstError<gr_ctx> fe;
+    for (const auto [b0, nb, s0] : grb::Segments{ first_slot, n_frames }) {
+        const grb::Prechecks pre(c, { b0, nb, s0 }, box_checks(c, kind != GR_CENTER_NAIVE));
         SlotUse use(c, s0, nb);
-        st = states_from_prechecks(c, nb, pre); if (st) return st;
+        st = states_from_prechecks(c, pre); if (st) return st;
         if (kind == GR_CENTER_NAIVE) st = center_stage(c, s0, nb, sel, 0, weighted, 0, 1);
         else if (kind == GR_CENTER_ESTIMATE) st = center_stage(c, s0, nb, sel, 1, weighted, 1, 1);
         else st = center_onepass_ok(c, sel) ? pbc_center_onepass(c, s0, nb, sel, weighted) : pbc_center_stages(c, s0, nb, sel, weighted);
@@ -1838,16 +1809,11 @@ int gr_group_center_batch(gr_ctx *c, uint32_t first_slot, uint32_t n_frames, con
         std::vector<GrFrameState> res;
         st = center_redo_fallbacks(c, s0, nb, sel, weighted, res); if (st) return st;   // (nothing to do unless the one-pass proof failed somewhere)
         for (uint32_t f = 0; f < nb; ++f) {
-            int s = pre[f];
-            if (s != GR_OK) c->err = msg[f];
-            else s = frame_status(c, res[f]);
-            if (s != GR_OK && first_err == GR_OK) { first_err = s; first_msg = c->err; first_idx = c->err_index; }
-            if (status_out) status_out[b0 + f] = s;
+            const int s = grb::close_frame(c, fe, pre, f, status_out, [&] { return frame_status(c, res[f]); });
             if (out) for (int k = 0; k < 3; ++k) out[3 * (size_t)(b0 + f) + k] = (s == GR_OK) ? res[f].com[k] : NAN;
         }
     }
-    if (first_err != GR_OK) { c->err = first_msg; c->err_index = first_idx; }
-    return first_err;
+    return fe.finish(c);
 } catch (...) { return gr_abi_guard(); }
 // atoms_center of the WHOLE system about a large contiguous reference group as ONE pass over HBM: the resident pass in its MODE 1 (gr_resident.h).
 // `done[f]` = 1: frame f is finished (its state is in c->state_host[f]); 0: the caller runs the two passes on it (the launch was not taken, never
@@ -1969,14 +1935,14 @@ static int center_resident(gr_ctx *c, uint32_t s0, uint32_t nb, const GrSel &all
     }
     return GR_OK;
 }
-// translate / wrap / centre a batch of frames: pre[] carries the host checks, frames that failed are left untouched
-static int translate_batch(gr_ctx *c, uint32_t s0, uint32_t nb, const Group *g, const float *v, int mode, int dim_mask,
-                           const std::vector<int> &pre, const std::vector<std::string> &msg, int *status_out, int &first_err, std::string &first_msg, uint64_t &first_idx) {
+// translate / wrap / centre the frames of `pre` (a segment or a run of one): frames that failed the host checks are left untouched
+static int translate_batch(gr_ctx *c, const grb::PreView &pre, const Group *g, const float *v, int mode, int dim_mask, int *status_out, grb::FirstError<gr_ctx> &fe) {
+    const uint32_t s0 = pre.s0, nb = pre.n;
     const GrSel sel = make_sel(*g);
     HIPCHK(c, hipMemsetAsync(c->bad_dev, 0xFF, 4 * (size_t)nb * sizeof(uint32_t), c->stream));
     // orthorhombic cells (every frame of the batch that will be touched): one float4 per lane, a 256-atom tile per workgroup (k_translate_wrap_rows)
     bool rows = g->n != 0 && sel.contiguous && c->translate_rows;
-    for (uint32_t f = 0; f < nb && rows; ++f) rows = pre[f] != GR_OK || c->boxes_host[s0 + f].ortho != 0;
+    for (uint32_t f = 0; f < nb && rows; ++f) rows = !pre.ok(f) || c->boxes_host[s0 + f].ortho != 0;
     if (rows) {
         const uint32_t tiles = ((sel.start + sel.n - 1u) >> 8) - (sel.start >> 8) + 1u;
         k_translate_wrap_rows<<<dim3(tiles * 3u, nb), dim3(64), 0, c->stream>>>(c->frames + (size_t)s0 * c->frame_stride, c->frame_stride, sel, c->boxes_dev + s0, c->state_dev, mode, dim_mask,
@@ -1992,14 +1958,11 @@ static int translate_batch(gr_ctx *c, uint32_t s0, uint32_t nb, const Group *g, 
     HIPCHK(c, hipMemcpyAsync(c->bad_host, c->bad_dev, 4 * (size_t)nb * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->state_host, c->state_dev, nb * sizeof(GrFrameState), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (uint32_t f = 0; f < nb; ++f) {
-        int s = pre[f];
-        if (s != GR_OK) c->err = msg[f];
-        else if (mode == 1 && c->state_host[f].status != GR_OK) s = frame_status(c, c->state_host[f]);
-        else if (c->bad_host[4 * f] != GR_NOIDX) s = fail(c, GR_E_NO_POSITION, "atom has no position", c->bad_host[4 * f]);
-        if (s != GR_OK && first_err == GR_OK) { first_err = s; first_msg = c->err; first_idx = c->err_index; }
-        if (status_out) status_out[f] = s;
-    }
+    for (uint32_t f = 0; f < nb; ++f)
+        grb::close_frame(c, fe, pre, f, status_out, [&]() -> int {
+            if (mode == 1 && c->state_host[f].status != GR_OK) return frame_status(c, c->state_host[f]);
+            return c->bad_host[4 * f] != GR_NOIDX ? fail(c, GR_E_NO_POSITION, "atom has no position", c->bad_host[4 * f]) : (int)GR_OK;
+        });
     return GR_OK;
 }
 static int translate_batch_api(gr_ctx *c, uint32_t first_slot, uint32_t n_frames, const char *group, const float *v, const char *center_group, int dim, int weighted, int *status_out) {
@@ -2009,62 +1972,51 @@ static int translate_batch_api(gr_ctx *c, uint32_t first_slot, uint32_t n_frames
     if (!g) return fail(c, GR_E_GROUP_NOT_FOUND, group);
     const Group *cg = nullptr;
     if (center_group) {
-        cg = find_group(c, center_group);
-        if (!cg) return fail(c, GR_E_GROUP_NOT_FOUND, center_group);
-        if (cg->n == 0) return fail(c, GR_E_EMPTY_GROUP, center_group);
+        cg = need_group(c, center_group, st, true); if (!cg) return st;
         if (dim < 0 || dim > 7) return fail(c, GR_E_INVALID_ARG, "bad dimension");
     }
     static const int mask[8] = { 0, 1, 2, 4, 3, 5, 6, 7 };
-    int first_err = GR_OK; std::string first_msg; uint64_t first_idx = 0;
-    for (uint32_t b0 = 0; b0 < n_frames; b0 += GR_MAX_BATCH) {
-        const uint32_t nb = std::min<uint32_t>(GR_MAX_BATCH, n_frames - b0), s0 = first_slot + b0;
-        std::vector<int> pre; std::vector<std::string> msg;
-        batch_prechecks(c, s0, nb, true, pre, msg);
+    grb::FirstError<gr_ctx> fe;
+    for (const auto [b0, nb, s0] : grb::Segments{ first_slot, n_frames }) {
+        const grb::Prechecks pre(c, { b0, nb, s0 }, box_checks(c, true));
         SlotUse use(c, s0, nb);
         // (where every frame passed the checks and the resident pass may take the batch, the states are not zeroed for it: its finalizers
         //  start from fresh ones; the two passes below get theirs when it turns out that they run)
-        bool states_unset = cg != nullptr;
-        for (uint32_t f = 0; f < nb; ++f) states_unset = states_unset && pre[f] == GR_OK;
-        if (!states_unset) { st = states_from_prechecks(c, nb, pre); if (st) return st; }
+        const bool states_unset = cg != nullptr && pre.all_ok;
+        if (!states_unset) { st = states_from_prechecks(c, pre); if (st) return st; }
         // atoms_center of the whole system about a large group: one pass over HBM where the resident pass takes it (center_resident); the frames
         // it did not finish -- all of them when it was not taken -- go through the two passes below, one run of consecutive frames at a time
         std::vector<uint8_t> done(nb, 0), torn(nb, 0);
         bool ran = false;
-        if (cg) { st = center_resident(c, s0, nb, make_sel(*g), make_sel(*cg), mask[dim], weighted, pre, states_unset, done, torn, ran); if (st) return st; }
+        if (cg) { st = center_resident(c, s0, nb, make_sel(*g), make_sel(*cg), mask[dim], weighted, pre.codes, states_unset, done, torn, ran); if (st) return st; }
         bool any_done = false;
         for (uint32_t f = 0; f < nb; ++f) any_done = any_done || done[f];
         if (any_done) {
             for (uint32_t f = 0; f < nb; ++f) {
                 if (!done[f]) continue;
-                int sf = pre[f];
-                if (sf != GR_OK) c->err = msg[f];
-                else if (torn[f]) sf = fail(c, GR_E_HIP, "the resident atoms_center pass stalled while this frame was being moved: some of its atoms carry the new coordinates, others the original ones (frame index in gr_last_error_index)", b0 + f);
-                else if (c->state_host[f].status != GR_OK) sf = frame_status(c, c->state_host[f]);
-                if (sf != GR_OK && first_err == GR_OK) { first_err = sf; first_msg = c->err; first_idx = c->err_index; }
-                if (status_out) status_out[b0 + f] = sf;
+                grb::close_frame(c, fe, pre, f, status_out, [&]() -> int {
+                    if (torn[f]) return fail(c, GR_E_HIP, "the resident atoms_center pass stalled while this frame was being moved: some of its atoms carry the new coordinates, others the original ones (frame index in gr_last_error_index)", pre.b0 + f);
+                    return frame_status(c, c->state_host[f]);
+                });
             }
             for (uint32_t a = 0; a < nb; ) {
                 if (done[a]) { ++a; continue; }
                 uint32_t b = a;
                 while (b < nb && !done[b]) ++b;
-                const std::vector<int> pre_run(pre.begin() + a, pre.begin() + b);
-                const std::vector<std::string> msg_run(msg.begin() + a, msg.begin() + b);
-                st = states_from_prechecks(c, b - a, pre_run); if (st) return st;
+                const grb::PreView run = pre.sub(a, b);
+                st = states_from_prechecks(c, run); if (st) return st;
                 st = center_stage(c, s0 + a, b - a, make_sel(*cg), 1, weighted, 1, 0); if (st) return st;
-                st = translate_batch(c, s0 + a, b - a, g, v, 1, mask[dim], pre_run, msg_run, status_out ? status_out + b0 + a : nullptr, first_err, first_msg, first_idx);
-                if (st) return st;
+                st = translate_batch(c, run, g, v, 1, mask[dim], status_out, fe); if (st) return st;
                 a = b;
             }
             continue;
         }
         // (a launch that handed every frame back left its internal statuses in state_dev: the two passes start from the prechecks again)
-        if (ran || states_unset) { st = states_from_prechecks(c, nb, pre); if (st) return st; }
+        if (ran || states_unset) { st = states_from_prechecks(c, pre); if (st) return st; }
         if (cg) { st = center_stage(c, s0, nb, make_sel(*cg), 1, weighted, 1, 0); if (st) return st; }   // group_estimate_center / _com per frame
-        st = translate_batch(c, s0, nb, g, v, cg ? 1 : 2, cg ? mask[dim] : 7, pre, msg, status_out ? status_out + b0 : nullptr, first_err, first_msg, first_idx);
-        if (st) return st;
+        st = translate_batch(c, pre, g, v, cg ? 1 : 2, cg ? mask[dim] : 7, status_out, fe); if (st) return st;
     }
-    if (first_err != GR_OK) { c->err = first_msg; c->err_index = first_idx; }
-    return first_err;
+    return fe.finish(c);
 }
 int gr_group_translate_batch(gr_ctx *c, uint32_t first_slot, uint32_t n_frames, const char *group, const float v[3], int *status_out) try {
     if (!c) return GR_E_INVALID_ARG;
@@ -2499,11 +2451,10 @@ static int segment_end(gr_rmsd_plan *p, float *rmsd_out, int *status_out, float 
     q.active = false;
     const uint32_t nb = q.nb, s0 = q.s0;
     const int fit = q.fit;
-    int first_err = GR_OK; uint64_t first_err_index = 0; std::string first_err_msg; uint64_t first_counts[2] = { 0, 0 };
-    auto note = [&](int s) { if (s != GR_OK && first_err == GR_OK) { first_err = s; first_err_index = c->err_index; first_err_msg = c->err; first_counts[0] = c->counts[0]; first_counts[1] = c->counts[1]; } };
+    grb::FirstError<gr_ctx> fe;
     if (!q.any_ok) {
         for (uint32_t f = 0; f < nb; ++f) {
-            c->err = q.pre_msg[f]; c->err_index = q.pre_idx[f]; note(q.pre[f]);
+            c->err = q.pre_msg[f]; c->err_index = q.pre_idx[f]; fe.note(c, q.pre[f]);
             if (status_out) status_out[f] = q.pre[f];
             if (rmsd_out) rmsd_out[f] = NAN;
             if (R_out) for (int k = 0; k < 9; ++k) R_out[9 * (size_t)f + k] = NAN;
@@ -2780,15 +2731,14 @@ static int segment_end(gr_rmsd_plan *p, float *rmsd_out, int *status_out, float 
             } else if (s != GR_OK) {
                 s = frame_status(c, res[f]);
             }
-            note(s);
+            fe.note(c, s);
             if (status_out) status_out[f] = s;
             if (rmsd_out) rmsd_out[f] = (s == GR_OK) ? res[f].rmsd : NAN;
             if (R_out) for (int k = 0; k < 9; ++k) R_out[9 * (size_t)f + k] = (s == GR_OK) ? res[f].R[k] : NAN;
         }
         if (final_states) *final_states = res;
     }
-    if (first_err != GR_OK) { c->err = first_err_msg; c->err_index = first_err_index; c->counts[0] = first_counts[0]; c->counts[1] = first_counts[1]; }
-    return first_err;
+    return fe.finish(c);
 }
 
 static int rmsd_batch_impl(gr_rmsd_plan *p, uint32_t first_slot, uint32_t n_frames, float *rmsd_out, int *status_out, float *R_out, int fit) {
@@ -2798,17 +2748,15 @@ static int rmsd_batch_impl(gr_rmsd_plan *p, uint32_t first_slot, uint32_t n_fram
     (void)hipSetDevice(c->device);
     if (p->pend.active) return fail(c, GR_E_INVALID_ARG, "a batch begun with gr_rmsd_batch_begin is still in flight");
     p->last_fallbacks = 0;
-    int first_err = GR_OK; uint64_t e_idx = 0; std::string e_msg; uint64_t e_cnt[2] = { 0, 0 };
-    for (uint32_t b0 = 0; b0 < n_frames; b0 += GR_MAX_BATCH) {
-        const uint32_t nb = std::min<uint32_t>(GR_MAX_BATCH, n_frames - b0);
-        st = segment_begin(p, first_slot + b0, nb, fit);
+    grb::FirstError<gr_ctx> fe;
+    for (const auto [b0, nb, s0] : grb::Segments{ first_slot, n_frames }) {
+        st = segment_begin(p, s0, nb, fit);
         if (st) { p->pend.active = false; resident_done(c); return st; }
         st = segment_end(p, rmsd_out ? rmsd_out + b0 : nullptr, status_out ? status_out + b0 : nullptr, R_out ? R_out + 9 * (size_t)b0 : nullptr);
-        if (st == GR_E_HIP) return st;
-        if (st != GR_OK && first_err == GR_OK) { first_err = st; e_idx = c->err_index; e_msg = c->err; e_cnt[0] = c->counts[0]; e_cnt[1] = c->counts[1]; }
+        if (st == GR_E_HIP) return st;      // (the only status of a segment that ends the call: every other one is its first failing frame's)
+        fe.note(c, st);
     }
-    if (first_err != GR_OK) { c->err = e_msg; c->err_index = e_idx; c->counts[0] = e_cnt[0]; c->counts[1] = e_cnt[1]; }
-    return first_err;
+    return fe.finish(c);
 }
 
 int gr_rmsd_batch_begin(gr_rmsd_plan *p, uint32_t first_slot, uint32_t n, int fit) try {

@@ -313,9 +313,7 @@ int gm_accumulate(gr_gridmap *m, uint32_t first_slot, uint32_t n_frames, const c
     (void)hipSetDevice(c->device);
     if (value < GR_GM_COUNT || value > GR_GM_Z) return fail(c, GR_E_INVALID_ARG, "grid map: unknown value");
     if (flags & ~(GR_GM_WRAP | GR_GM_FORCE_GLOBAL)) return fail(c, GR_E_INVALID_ARG, "grid map: unknown flag");
-    const Group *g = find_group(c, group);
-    if (!g) return fail(c, GR_E_GROUP_NOT_FOUND, group ? group : "(null)");
-    if (g->n == 0) return fail(c, GR_E_EMPTY_GROUP, group);
+    const Group *g = need_group(c, group, st, true); if (!g) return st;
     const GrSel sel = make_sel(*g);
     const int form = sel.contiguous ? 0 : (sel.masked & 1u) ? 2 : 1;
     const bool wrap = (flags & GR_GM_WRAP) != 0;
@@ -335,19 +333,15 @@ int gm_accumulate(gr_gridmap *m, uint32_t first_slot, uint32_t n_frames, const c
     P.x0 = m->span_x[0]; P.tx = m->tile[0]; P.y0 = m->span_y[0]; P.ty = m->tile[1];
     P.nx = (uint32_t)m->nx; P.ny = (uint32_t)m->ny; P.n_tiles = n_tiles; P.value = value; P.wrap = wrap ? 1 : 0;
     P.count = m->count_dev; P.sum = m->sum_dev; P.n_out = m->nout_dev; P.offset = offset ? m->off_dev : nullptr; P.verdict = m->verdict_dev;
-    int first_err = GR_OK; std::string first_msg; uint64_t first_idx = 0;
-    for (uint32_t b0 = 0; b0 < n_frames; b0 += GR_MAX_BATCH) {
-        const uint32_t nb = std::min<uint32_t>(GR_MAX_BATCH, n_frames - b0), s0 = first_slot + b0;
-        std::vector<int> pre; std::vector<std::string> msg;
-        batch_prechecks(c, s0, nb, wrap, pre, msg);
-        bool any_ok = false;
+    grb::FirstError<gr_ctx> fe;
+    for (const auto [b0, nb, s0] : grb::Segments{ first_slot, n_frames }) {
+        const grb::Prechecks pre(c, { b0, nb, s0 }, box_checks(c, wrap));
         for (uint32_t f = 0; f < nb; ++f) {
-            any_ok = any_ok || pre[f] == GR_OK;
-            m->verdict_host[f] = pre[f] == GR_OK ? GR_NOIDX : GR_GM_SKIP;
+            m->verdict_host[f] = pre.ok(f) ? GR_NOIDX : GR_GM_SKIP;
             m->off_host[f] = offset ? offset[b0 + f] : 0.0f;
             m->nout_host[f] = 0ull;
         }
-        if (any_ok) {
+        if (pre.any_ok) {
             SlotUse use(c, s0, nb);
             HIPCHK(c, hipMemcpyAsync(m->verdict_dev, m->verdict_host, nb * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
             if (offset) HIPCHK(c, hipMemcpyAsync(m->off_dev, m->off_host, nb * sizeof(float), hipMemcpyHostToDevice, c->stream));
@@ -363,16 +357,11 @@ int gm_accumulate(gr_gridmap *m, uint32_t first_slot, uint32_t n_frames, const c
             HIPCHK(c, hipStreamSynchronize(c->stream));
         }
         for (uint32_t f = 0; f < nb; ++f) {
-            int s = pre[f];
-            if (s != GR_OK) c->err = msg[f];
-            else if (m->verdict_host[f] != GR_NOIDX) s = fail(c, GR_E_NO_POSITION, "atom has no position", m->verdict_host[f]);
-            if (s != GR_OK && first_err == GR_OK) { first_err = s; first_msg = c->err; first_idx = c->err_index; }
-            if (status_out) status_out[b0 + f] = s;
+            const int s = grb::close_frame(c, fe, pre, f, status_out, [&] { return m->verdict_host[f] != GR_NOIDX ? fail(c, GR_E_NO_POSITION, "atom has no position", m->verdict_host[f]) : (int)GR_OK; });
             if (n_outside) n_outside[b0 + f] = s == GR_OK ? m->nout_host[f] : 0ull;
         }
     }
-    if (first_err != GR_OK) { c->err = first_msg; c->err_index = first_idx; }
-    return first_err;
+    return fe.finish(c);
 }
 
 }  // namespace

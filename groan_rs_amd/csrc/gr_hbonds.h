@@ -390,14 +390,12 @@ int gr_hbond_batch(gr_hbond_plan *p, uint32_t first_slot, uint32_t n_frames, uin
     (void)hipSetDevice(c->device);
     const uint32_t nf = n_frames, np = p->n_pairs, nl = p->n_lanes, na = p->n_acc, s0 = first_slot;
     // host checks and the batch's key space
-    std::vector<int> pre(nf, GR_OK);
-    std::vector<std::string> msg(nf);
+    const grb::Prechecks pre(c, { 0, nf, s0 }, [&](uint32_t slot) { return hb_box_check(c, slot); });
     std::vector<GrHbFrame> frs(nf);
     uint64_t nkeys = 0;
     for (uint32_t f = 0; f < nf; ++f) {
         memset(&frs[f], 0, sizeof(GrHbFrame));
-        pre[f] = hb_box_check(c, s0 + f);
-        if (pre[f] != GR_OK) { msg[f] = c->err; continue; }
+        if (!pre.ok(f)) continue;
         frs[f].g = hb_grid(c->boxes_host[s0 + f], p->cutoff, p->max_chain_acc);
         frs[f].kbase = (uint32_t)nkeys; frs[f].ok = 1;
         nkeys += (uint64_t)p->n_chains * frs[f].g.ncells;
@@ -450,18 +448,15 @@ int gr_hbond_batch(gr_hbond_plan *p, uint32_t first_slot, uint32_t n_frames, uin
     const unsigned long long *rb_offs = (const unsigned long long *)rb_h, *rb_dbad = (const unsigned long long *)(rb_h + (o_dbad - o_rb));
     const uint32_t *rb_abad = (const uint32_t *)(rb_h + (o_abad - o_rb));
     // frames' statuses: box checks, then acceptors (grid construction), then the walk's first donor / hydrogen
-    int first_err = GR_OK; std::string first_msg; uint64_t first_idx = 0;
-    for (uint32_t f = 0; f < nf; ++f) {
-        int s = pre[f]; std::string m = msg[f]; uint64_t idx = 0;
-        if (s == GR_OK && rb_abad[f] != GR_NOIDX) { s = GR_E_NO_POSITION; m = "atom has no position"; idx = p->acc_atom[rb_abad[f]]; }
-        else if (s == GR_OK && rb_dbad[f] != ~0ull) {
+    grb::FirstError<gr_ctx> fe;
+    for (uint32_t f = 0; f < nf; ++f)
+        grb::close_frame(c, fe, pre, f, status_out, [&]() -> int {
+            if (rb_abad[f] != GR_NOIDX) return fail(c, GR_E_NO_POSITION, "atom has no position", p->acc_atom[rb_abad[f]]);
+            if (rb_dbad[f] == ~0ull) return GR_OK;
             const GrHbLane &L = p->lanes[(uint32_t)(rb_dbad[f] >> 32)];
             const uint32_t k = (uint32_t)rb_dbad[f];
-            s = GR_E_NO_POSITION; m = "atom has no position"; idx = k == 0xFFFFFFFFu ? L.donor : p->hyd[L.h0 + k];
-        }
-        if (status_out) status_out[f] = s;
-        if (s != GR_OK && first_err == GR_OK) { first_err = s; first_msg = m; first_idx = idx; }
-    }
+            return fail(c, GR_E_NO_POSITION, "atom has no position", k == 0xFFFFFFFFu ? L.donor : p->hyd[L.h0 + k]);
+        });
     const unsigned long long total = rb_offs[n_rb - 1];
     memcpy(offsets, rb_offs, 8 * n_rb);
     if (n_total) *n_total = total;
@@ -480,8 +475,7 @@ int gr_hbond_batch(gr_hbond_plan *p, uint32_t first_slot, uint32_t n_frames, uin
         HIPCHK(c, hipMemcpyAsync(angle, o_ang, 4 * total, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
-    if (first_err != GR_OK) { c->err = first_msg; c->err_index = first_idx; }
-    return first_err;
+    return fe.finish(c);
 } catch (...) { return gr_abi_guard(); }
 
 }  // extern "C"

@@ -215,21 +215,17 @@ int molecules_whole_batch(gr_ctx *c, uint32_t first_slot, uint32_t n_frames, int
     const uint32_t chunk = (uint32_t)std::max<uint64_t>(1, GR_WHOLE_CHUNK_BYTES / frame_bytes);
     const uint32_t n_groups = (uint32_t)(c->n_pad >> 2), n_tiles = (uint32_t)(c->n_pad >> 8);
     const uint32_t check_wgs = std::min<uint32_t>((n_groups + 255u) / 256u, 4096u);
-    int first_err = GR_OK; std::string first_msg; uint64_t first_idx = 0;
-    for (uint32_t b0 = 0; b0 < n_frames; b0 += GR_MAX_BATCH) {
-        const uint32_t nb = std::min<uint32_t>(GR_MAX_BATCH, n_frames - b0), s0 = first_slot + b0;
-        std::vector<int> pre; std::vector<std::string> msg;
-        batch_prechecks(c, s0, nb, true, pre, msg);           // simbox_check first, even without bonds (modifying.rs:343-344)
-        bool any_ok = false;
-        for (uint32_t f = 0; f < nb; ++f) any_ok = any_ok || pre[f] == GR_OK;
-        if (any_mol && any_ok) {
+    grb::FirstError<gr_ctx> fe;
+    for (const auto [b0, nb, s0] : grb::Segments{ first_slot, n_frames }) {
+        const grb::Prechecks pre(c, { b0, nb, s0 }, box_checks(c, true));           // simbox_check first, even without bonds (modifying.rs:343-344)
+        if (any_mol && pre.any_ok) {
             SlotUse use(c, s0, nb);
-            for (uint32_t f = 0; f < nb; ++f) W.words_host[f] = pre[f] == GR_OK ? GR_WHOLE_CLEAR : GR_WHOLE_SKIP;
+            for (uint32_t f = 0; f < nb; ++f) W.words_host[f] = pre.ok(f) ? GR_WHOLE_CLEAR : GR_WHOLE_SKIP;
             HIPCHK(c, hipMemcpyAsync(W.words_dev, W.words_host, nb * sizeof(unsigned long long), hipMemcpyHostToDevice, c->stream));
             for (uint32_t a = 0; a < nb; a += chunk) {
                 const uint32_t k = std::min(chunk, nb - a);
                 bool tric = false;
-                for (uint32_t f = a; f < a + k; ++f) tric = tric || (pre[f] == GR_OK && !c->boxes_host[s0 + f].ortho);
+                for (uint32_t f = a; f < a + k; ++f) tric = tric || (pre.ok(f) && !c->boxes_host[s0 + f].ortho);
                 const int keep_far = tric && W.n_far ? 1 : 0;
                 k_whole_check<<<dim3(check_wgs, k), dim3(256), 0, c->stream>>>(c->frames, c->frame_stride, s0 + a, n_groups, W.map_dev, W.rank_dev, W.words_dev + a);
                 k_whole_place<<<dim3(n_tiles, k), dim3(64), 0, c->stream>>>(c->frames, c->frame_stride, s0 + a, W.map_dev, W.words_dev + a, c->boxes_dev, keep_far);
@@ -241,53 +237,37 @@ int molecules_whole_batch(gr_ctx *c, uint32_t first_slot, uint32_t n_frames, int
             HIPCHK(c, hipMemcpyAsync(W.words_host, W.words_dev, nb * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
         }
-        for (uint32_t f = 0; f < nb; ++f) {
-            int s = pre[f];
-            if (s != GR_OK) c->err = msg[f];
-            else if (any_mol && W.words_host[f] != GR_WHOLE_CLEAR) {
+        for (uint32_t f = 0; f < nb; ++f)
+            grb::close_frame(c, fe, pre, f, status_out, [&]() -> int {
+                if (!any_mol || W.words_host[f] == GR_WHOLE_CLEAR) return GR_OK;
                 const uint64_t ref = W.words_host[f] >> 32, rk = W.words_host[f] & 0xFFFFFFFFull;
-                s = fail(c, GR_E_NO_POSITION, "atom has no position", W.topo.mol_atom(W.topo.mol_of[ref], rk));
-            }
-            if (s != GR_OK && first_err == GR_OK) { first_err = s; first_msg = c->err; first_idx = c->err_index; }
-            if (status_out) status_out[b0 + f] = s;
-        }
+                return fail(c, GR_E_NO_POSITION, "atom has no position", W.topo.mol_atom(W.topo.mol_of[ref], rk));
+            });
     }
-    if (first_err != GR_OK) { c->err = first_msg; c->err_index = first_idx; }
-    return first_err;
+    return fe.finish(c);
 }
 
 int group_whole_batch(gr_ctx *c, uint32_t first_slot, uint32_t n_frames, const char *group, int *status_out) {
     int st = slot_check(c, first_slot, n_frames); if (st) return st;
     (void)hipSetDevice(c->device);
     // group_estimate_center first (modifying.rs:449): its checks in its order -- group exists, non-empty, box, positions
-    const Group *g = find_group(c, group);
-    if (!g) return fail(c, GR_E_GROUP_NOT_FOUND, group ? group : "(null)");
-    if (g->n == 0) return fail(c, GR_E_EMPTY_GROUP, group);
+    const Group *g = need_group(c, group, st, true); if (!g) return st;
     const GrSel sel = make_sel(*g);
     const int form = sel.contiguous ? 0 : (sel.masked & 1u) ? 2 : 1;
     const uint64_t units = form == 1 ? (uint64_t)sel.n : ((uint64_t)(form == 0 ? sel.n : sel.span) + 3) / 4 + 1;
     const uint32_t nwg = (uint32_t)std::min<uint64_t>((units + 255) / 256, 4096);
-    int first_err = GR_OK; std::string first_msg; uint64_t first_idx = 0;
-    for (uint32_t b0 = 0; b0 < n_frames; b0 += GR_MAX_BATCH) {
-        const uint32_t nb = std::min<uint32_t>(GR_MAX_BATCH, n_frames - b0), s0 = first_slot + b0;
-        std::vector<int> pre; std::vector<std::string> msg;
-        batch_prechecks(c, s0, nb, true, pre, msg);
+    grb::FirstError<gr_ctx> fe;
+    for (const auto [b0, nb, s0] : grb::Segments{ first_slot, n_frames }) {
+        const grb::Prechecks pre(c, { b0, nb, s0 }, box_checks(c, true));
         SlotUse use(c, s0, nb);
-        st = states_from_prechecks(c, nb, pre); if (st) return st;
+        st = states_from_prechecks(c, pre); if (st) return st;
         st = center_stage(c, s0, nb, sel, 1, 0, 1, 1); if (st) return st;      // as gr_group_center_batch(GR_CENTER_ESTIMATE, weighted 0)
         k_group_whole<<<dim3(nwg, nb), dim3(256), 0, c->stream>>>(c->frames, c->frame_stride, s0, sel, c->boxes_dev, c->state_dev, form);
         HIPCHK(c, hipGetLastError());
         st = fetch_states(c, nb); if (st) return st;
-        for (uint32_t f = 0; f < nb; ++f) {
-            int s = pre[f];
-            if (s != GR_OK) c->err = msg[f];
-            else s = frame_status(c, c->state_host[f]);
-            if (s != GR_OK && first_err == GR_OK) { first_err = s; first_msg = c->err; first_idx = c->err_index; }
-            if (status_out) status_out[b0 + f] = s;
-        }
+        for (uint32_t f = 0; f < nb; ++f) grb::close_frame(c, fe, pre, f, status_out, [&] { return frame_status(c, c->state_host[f]); });
     }
-    if (first_err != GR_OK) { c->err = first_msg; c->err_index = first_idx; }
-    return first_err;
+    return fe.finish(c);
 }
 
 }  // namespace
