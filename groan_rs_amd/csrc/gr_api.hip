@@ -15,6 +15,8 @@
 
 #include "../../include/groan_hip.h"
 #include "gr_batch.h"
+#include "gr_buf.h"
+#include "gr_workers.h"
 #include "gr_container.h"
 #include "gr_kernels.h"
 #include "gr_hot.h"
@@ -87,8 +89,7 @@ struct gr_ctx {
     // workspace
     GrCenPartial *cen_partials = nullptr;
     GrAccPartial *acc_partials = nullptr;
-    double *fit_partials = nullptr;   // [frames of a segment][fit workgroups per frame]: sum w |R q - p|^2 of k_fit<true>
-    size_t fit_partials_cap = 0;
+    grbuf::Dev<double> fit_partials;  // [frames of a segment][fit workgroups per frame]: sum w |R q - p|^2 of k_fit<true>
     int two_pass = 1;                 // GR_TUNE_TWO_PASS 0: RMSD-fit keeps the closed-form single-pass rmsd (k_rmsd_accum<0>)
     int masked_sel = 1;               // GR_TUNE_MASKED_SELECTIONS 0: dense scattered selections keep to their gather lists (groups built afterwards)
     int rmsd_fast = 1;                // GR_TUNE_RMSD_FAST 0: the RMSD without fit always takes the exact-product pass (k_rmsd_accum<0>)
@@ -125,7 +126,7 @@ struct gr_ctx {
     uint32_t res_test_abort_at = 0xFFFFFFFFu;   // GR_TUNE_TEST_RESIDENT_ABORT_AT (tests): the finalizer of this frame of the next resident launch raises `abort`
     uint32_t res_skip = 0, res_backoff = 0;     // segments the pass sits out after a missed start handshake (doubles with every miss in a row)
     uint32_t *res_progress = nullptr;           // [GR_MAX_CHUNKS][8]: frames each streaming wave of the last resident launch had fitted when it left
-    unsigned long long *res_wgrec = nullptr; size_t res_wgrec_cap = 0;   // [frames][streaming workgroups, padded to 16][32] tagged words
+    grbuf::Dev<unsigned long long> res_wgrec;   // [frames][streaming workgroups, padded to 16][32] tagged words
     unsigned long long *res_rec = nullptr;   // [GR_MAX_BATCH][16]
     uint32_t *res_abort = nullptr;    // device word
     uint32_t *res_words_host = nullptr;   // the control words of the last resident launch as res_collect took them out of res_out (8, 9: this launch's share)
@@ -138,7 +139,7 @@ struct gr_ctx {
     uint32_t res_late_seen[2] = { 0, 0 };       // res_abort[8], [9] (running sums) as the last launch left them
     uint64_t res_lean_segments = 0, res_sync_fallbacks = 0;   // gr_ctx_stat: resident launches that started from fresh states; polls that gave up and synchronised the stream
     GrShapeSet *shape_set_dev = nullptr;      // the shapes of the geometry selection in flight (k_shape_mask reads them through a uniform pointer)
-    unsigned long long *shape_mask_dev = nullptr, *shape_mask_host = nullptr; size_t shape_mask_cap = 0;   // geometry selection: one bit per atom of the source group (device, pinned host), grown on demand
+    grbuf::Dev<unsigned long long> shape_mask_dev; grbuf::Pinned<unsigned long long> shape_mask_host;   // geometry selection: one bit per atom of the source group (device, pinned host), grown on demand
     uint32_t res_epoch = 0;
     bool res_in_use = false;          // the pending segment took the resident pass (segment_end checks the abort word)
     uint64_t res_launches = 0, res_handshake_misses = 0, res_aborts = 0, res_redone_frames = 0;   // gr_ctx_stat
@@ -153,7 +154,7 @@ struct gr_ctx {
     uint64_t small_calls = 0, small_sync_fallbacks = 0;                // gr_ctx_stat
     uint32_t *bad_dev = nullptr;          // [4 * GR_MAX_BATCH]: per frame, first atom without position (rows / columns)
     uint32_t *bad_host = nullptr;         // pinned, same size
-    float *pd_out = nullptr; size_t pd_cap = 0;
+    grbuf::Dev<float> pd_out;         // the pair-distance calls' output
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // per-kernel HIP-event profile of the batched RMSD path (gr_profile_*): 0 accumulate, 1 finalize, 2 fit
     hipEvent_t pev[6 * GR_MAX_BATCH] = {};   // per group: begin / end of the sums, finalize and fit kernels
@@ -173,15 +174,15 @@ struct gr_ctx {
     // device-side xtc unpacking (gr_xtc_read_frames_device): grow-only staging, pinned host mirror + device copy
     // two pinned staging banks used in turn: the host reads + skims batch k + 1 while the H2D copy of batch k drains the other
     // and two device banks: the H2D copy of batch k + 1 (copy stream) runs beside k_xtc_unpack of batch k (unpack stream)
-    unsigned char *xtc_host[2] = { nullptr, nullptr }, *xtc_dev[2] = { nullptr, nullptr }; size_t xtc_host_cap[2] = { 0, 0 }, xtc_dev_cap[2] = { 0, 0 };
+    grbuf::Pinned<unsigned char> xtc_host[2]; grbuf::Dev<unsigned char> xtc_dev[2];
     hipEvent_t xtc_ev[2] = { nullptr, nullptr };        // the bank's last H2D has left the pinned bank / filled the device bank
     hipEvent_t xtc_unpacked[2] = { nullptr, nullptr };  // the bank's last unpack kernel has finished with the device bank
     hipStream_t unpack_stream = nullptr;
     uint32_t xtc_bank = 0;
-    float *wr_host = nullptr; size_t wr_cap = 0;   // pinned landing buffer of gr_xtc_write_slots (grow-only)
+    grbuf::Pinned<float> wr_host;   // pinned landing buffer of gr_xtc_write_slots (grow-only)
     // device xtc encoder (gr_xtc_enc_dev.h), grow-only: quantised atoms, run words, run descriptors, streams
-    void *xe_dev[6] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr }; size_t xe_cap[6] = { 0, 0, 0, 0, 0, 0 };   // ints, enc, runs, meta, hdr + offsets, out
-    unsigned char *xe_host[2] = { nullptr, nullptr }; size_t xe_host_cap[2] = { 0, 0 };     // pinned, two banks (rounds in turn): headers + offsets + streams
+    grbuf::Dev<unsigned char> xe_dev[6];   // ints, enc, runs, meta, hdr + offsets, out
+    grbuf::Pinned<unsigned char> xe_host[2];     // pinned, two banks (rounds in turn): headers + offsets + streams
     int xtc_dev_encode = 1;           // GR_TUNE_XTC_DEVICE_ENCODE
     uint64_t xtc_dev_frames = 0;      // frames gr_xtc_write_slots compressed on the device (GR_STAT_XTC_DEVICE_FRAMES)
     int strict = 0;
@@ -553,6 +554,12 @@ static hipError_t sync_ingest(gr_ctx *c) {
     if (e == hipSuccess && c->unpack_stream) e = hipStreamSynchronize(c->unpack_stream);
     return e;
 }
+// boxes_host[slot] is about to be rewritten (box_fill): the slot's previous box copy must have left it (see gr_frame_upload)
+static int slot_box_wait(gr_ctx *c, uint32_t slot) {
+    if (c->ev_ready[slot]) HIPCHK(c, hipEventSynchronize(c->ev_ready[slot]));
+    else HIPCHK(c, hipEventCreateWithFlags(&c->ev_ready[slot], hipEventDisableTiming));
+    return GR_OK;
+}
 // host half of set_box: boxes_host[slot] + the slot's box status; the caller copies boxes_host to boxes_dev
 void box_fill(gr_ctx *c, uint32_t slot, const float *box9) {
     GrBox &b = c->boxes_host[slot];
@@ -661,12 +668,21 @@ static int small_wait(gr_ctx *c, uint32_t seq, uint32_t words = 1) {
 static int res_next_epoch(gr_ctx *c, uint32_t *epoch) {
     if (++c->res_epoch == 0u) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (c->res_wgrec) HIPCHK(c, hipMemset(c->res_wgrec, 0, c->res_wgrec_cap * sizeof(unsigned long long)));
+        if (c->res_wgrec.get()) HIPCHK(c, hipMemset(c->res_wgrec.get(), 0, c->res_wgrec.cap() * sizeof(unsigned long long)));
         HIPCHK(c, hipMemset(c->res_rec, 0, (size_t)GR_MAX_BATCH * 16 * sizeof(unsigned long long)));
         HIPCHK(c, hipMemset(c->res_abort + 2, 0, 2 * sizeof(uint32_t)));
         c->res_epoch = 1u;
     }
     *epoch = c->res_epoch;
+    return GR_OK;
+}
+// the streaming workgroups' tagged words of a launch: a new block is cleared on the launch's stream (tag 0 = no launch)
+static int res_wgrec_reserve(gr_ctx *c, size_t rec_words, hipStream_t S) {
+    bool grew = false;
+    HIPCHK(c, c->res_wgrec.reserve(rec_words, grbuf::exact, &grew));
+    const hipError_t e = grew ? hipMemsetAsync(c->res_wgrec.get(), 0, rec_words * sizeof(unsigned long long), S) : hipSuccess;
+    if (e != hipSuccess) c->res_wgrec.release();      // (never launch on a block that was not cleared: the next call allocates again)
+    HIPCHK(c, e);
     return GR_OK;
 }
 // tests (GR_TUNE_TEST_RESIDENT_NO_START): the launch of this epoch finds its start verdict already "never started"
@@ -938,15 +954,11 @@ void gr_ctx_destroy(gr_ctx *c) try {
     if (c->boxes_host) (void)hipHostFree(c->boxes_host);
     if (c->cen_partials) (void)hipFree(c->cen_partials);
     if (c->acc_partials) (void)hipFree(c->acc_partials);
-    if (c->fit_partials) (void)hipFree(c->fit_partials);
     if (c->fuse_cnt) (void)hipFree(c->fuse_cnt);
     if (c->res_abort) (void)hipFree(c->res_abort);
     if (c->res_words_host) (void)hipHostFree(c->res_words_host);
     if (c->res_out) (void)hipHostFree(c->res_out);
     if (c->shape_set_dev) (void)hipFree(c->shape_set_dev);
-    if (c->shape_mask_dev) (void)hipFree(c->shape_mask_dev);
-    if (c->shape_mask_host) (void)hipHostFree(c->shape_mask_host);
-    if (c->res_wgrec) (void)hipFree(c->res_wgrec);
     if (c->res_rec) (void)hipFree(c->res_rec);
     if (c->res_progress) (void)hipFree(c->res_progress);
     if (c->state_dev) (void)hipFree(c->state_dev);
@@ -954,17 +966,11 @@ void gr_ctx_destroy(gr_ctx *c) try {
     if (c->small_state) (void)hipHostFree(c->small_state);
     if (c->bad_dev) (void)hipFree(c->bad_dev);
     if (c->bad_host) (void)hipHostFree(c->bad_host);
-    if (c->pd_out) (void)hipFree(c->pd_out);
-    for (int k = 0; k < 6; ++k) if (c->xe_dev[k]) (void)hipFree(c->xe_dev[k]);
-    for (int k = 0; k < 2; ++k) if (c->xe_host[k]) (void)hipHostFree(c->xe_host[k]);
     if (c->unpack_stream) { (void)hipStreamSynchronize(c->unpack_stream); (void)hipStreamDestroy(c->unpack_stream); }
     for (int k = 0; k < 2; ++k) {
-        if (c->xtc_host[k]) (void)hipHostFree(c->xtc_host[k]);
-        if (c->xtc_dev[k]) (void)hipFree(c->xtc_dev[k]);
         if (c->xtc_ev[k]) (void)hipEventDestroy(c->xtc_ev[k]);
         if (c->xtc_unpacked[k]) (void)hipEventDestroy(c->xtc_unpacked[k]);
     }
-    if (c->wr_host) (void)hipHostFree(c->wr_host);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     for (int k = 0; k < 6 * GR_MAX_BATCH; ++k) if (c->pev[k]) (void)hipEventDestroy(c->pev[k]);
@@ -972,7 +978,7 @@ void gr_ctx_destroy(gr_ctx *c) try {
     for (int k = 0; k < 64; ++k) if (c->ev_done_ring[k]) (void)hipEventDestroy(c->ev_done_ring[k]);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;      // (frees the grow-only buffers, gr_buf.h: the device is set and the streams have been synchronised above)
 } catch (...) { }
 
 const char *gr_last_error(const gr_ctx *c) { return c ? c->err.c_str() : "null context"; }
@@ -1085,8 +1091,7 @@ int gr_frame_upload(gr_ctx *c, uint32_t slot, const float *xyz, const float *box
     // boxes_host[slot] is the pinned SOURCE of the slot's previous box copy, which sits on the copy stream behind that
     // upload's 12 MB frame copy: it may only be rewritten once that copy has run -- whether or not a compute call has
     // meanwhile consumed the "upload pending" flag (upload -> batch_begin -> upload again into the same slot)
-    if (c->ev_ready[slot]) HIPCHK(c, hipEventSynchronize(c->ev_ready[slot]));
-    else HIPCHK(c, hipEventCreateWithFlags(&c->ev_ready[slot], hipEventDisableTiming));
+    st = slot_box_wait(c, slot); if (st) return st;
     // the slot may still be read by kernels issued earlier: order the copy behind the last compute call that used it
     // (events of one stream complete in order, so a recycled ring entry only makes the wait conservative)
     if (c->slot_gen[slot]) HIPCHK(c, hipStreamWaitEvent(c->copy_stream, c->ev_done_ring[c->slot_gen[slot] % 64], 0));
@@ -1277,16 +1282,6 @@ static int pairdist_run(gr_ctx *c, uint32_t slot, const GrSel &s1, const GrSel &
     return pairdist_status(c, 0, s1);
 }
 
-static int pairdist_reserve(gr_ctx *c, size_t need) {
-    if (need > c->pd_cap) {
-        if (c->pd_out) (void)hipFree(c->pd_out);
-        c->pd_out = nullptr; c->pd_cap = 0;
-        HIPCHK(c, hipMalloc(&c->pd_out, (need ? need : 1) * sizeof(float)));
-        c->pd_cap = need;
-    }
-    return GR_OK;
-}
-
 int gr_group_all_distances_batch_device(gr_ctx *c, uint32_t first_slot, uint32_t n_frames, const char *g1, const char *g2, int dim,
                                         float **out_dev, uint64_t *n1, uint64_t *n2, int *status_out) try {
     int st = slot_check(c, first_slot, n_frames); if (st) return st;
@@ -1295,15 +1290,15 @@ int gr_group_all_distances_batch_device(gr_ctx *c, uint32_t first_slot, uint32_t
     const Group *b = need_group(c, g2, st); if (!b) return st;
     if (dim < 0 || dim > 7) return fail(c, GR_E_INVALID_ARG, "bad dimension");
     const size_t per = (size_t)a->n * b->n;
-    st = pairdist_reserve(c, per * n_frames); if (st) return st;
+    HIPCHK(c, c->pd_out.reserve(per * n_frames, grbuf::exact));
     const GrSel s1 = make_sel(*a), s2 = make_sel(*b);
     grb::FirstError<gr_ctx> fe;
     for (const auto [b0, nb, s0] : grb::Segments{ first_slot, n_frames }) {
         const grb::Prechecks pre(c, { b0, nb, s0 }, box_checks(c, true));
-        st = pairdist_launch(c, s0, nb, s1, s2, dim, c->pd_out + (size_t)b0 * per, per); if (st) return st;
+        st = pairdist_launch(c, s0, nb, s1, s2, dim, c->pd_out.get() + (size_t)b0 * per, per); if (st) return st;
         for (uint32_t f = 0; f < nb; ++f) grb::close_frame(c, fe, pre, f, status_out, [&] { return pairdist_status(c, f, s1); });
     }
-    if (out_dev) *out_dev = c->pd_out;
+    if (out_dev) *out_dev = c->pd_out.get();
     if (n1) *n1 = a->n;
     if (n2) *n2 = b->n;
     return fe.finish(c);
@@ -1317,9 +1312,9 @@ int gr_group_all_distances_device(gr_ctx *c, uint32_t slot, const char *g1, cons
     const Group *b = need_group(c, g2, st); if (!b) return st;
     st = box_check(c, slot); if (st) return st;
     if (dim < 0 || dim > 7) return fail(c, GR_E_INVALID_ARG, "bad dimension");
-    st = pairdist_reserve(c, (size_t)a->n * b->n); if (st) return st;
-    st = pairdist_run(c, slot, make_sel(*a), make_sel(*b), dim, c->pd_out); if (st) return st;
-    if (out_dev) *out_dev = c->pd_out;
+    HIPCHK(c, c->pd_out.reserve((size_t)a->n * b->n, grbuf::exact));
+    st = pairdist_run(c, slot, make_sel(*a), make_sel(*b), dim, c->pd_out.get()); if (st) return st;
+    if (out_dev) *out_dev = c->pd_out.get();
     if (n1) *n1 = a->n;
     if (n2) *n2 = b->n;
     return GR_OK;
@@ -1373,15 +1368,15 @@ int gr_group_all_distances_reduce_batch(gr_ctx *c, uint32_t first_slot, uint32_t
     std::vector<uint32_t> host;
     std::vector<unsigned long long> host64;
     for (const auto [b0, nb, s0] : grb::Segments{ first_slot, n_frames }) {
-        st = pairdist_reserve(c, ((size_t)nb * words * (word_bytes / sizeof(float)) + 1) & ~(size_t)1); if (st) return st;
-        uint32_t *acc = reinterpret_cast<uint32_t *>(c->pd_out);
+        HIPCHK(c, c->pd_out.reserve(((size_t)nb * words * (word_bytes / sizeof(float)) + 1) & ~(size_t)1, grbuf::exact));
+        uint32_t *acc = reinterpret_cast<uint32_t *>(c->pd_out.get());
         HIPCHK(c, hipMemsetAsync(acc, op == GR_PD_MIN ? 0xFF : 0x00, (size_t)nb * words * word_bytes, c->stream));
         const grb::Prechecks pre(c, { b0, nb, s0 }, box_checks(c, true));
         // per row of a group of some size: the groups change places and every lane keeps the values of its own four atoms (k_pairdist,
         // "transposed"); a handful of rows against many columns stays as it is (the lanes are the columns)
         const bool transposed = per_row && a->n >= 512;
         const GrPdRed red = { op, per_row ? (transposed ? 2 : 1) : 0, op == GR_PD_HIST ? (float)nbins / param : param, nbins, acc64 ? nullptr : acc,
-                              acc64 ? reinterpret_cast<unsigned long long *>(c->pd_out) : nullptr, words };
+                              acc64 ? reinterpret_cast<unsigned long long *>(c->pd_out.get()) : nullptr, words };
         st = transposed ? pairdist_launch(c, s0, nb, s2, s1, dim, nullptr, 0, &red) : pairdist_launch(c, s0, nb, s1, s2, dim, nullptr, 0, &red); if (st) return st;
         if (transposed) for (uint32_t f = 0; f < nb; ++f) std::swap(c->bad_host[4 * f], c->bad_host[4 * f + 1]);      // (first bad atom among the rows / the columns)
         if (acc64) { host64.resize((size_t)nb * words); HIPCHK(c, hipMemcpyAsync(host64.data(), acc, host64.size() * word_bytes, hipMemcpyDeviceToHost, c->stream)); }
@@ -1424,10 +1419,10 @@ int gr_atoms_distance(gr_ctx *c, uint32_t slot, uint64_t i1, uint64_t i2, int di
     st = box_check(c, slot); if (st) return st;
     if (dim < 0 || dim > 7) return fail(c, GR_E_INVALID_ARG, "bad dimension");
     GrSel s1 = { 1u, 1u, (uint32_t)i1, (uint32_t)i1 >> 8, nullptr }, s2 = { 1u, 1u, (uint32_t)i2, (uint32_t)i2 >> 8, nullptr };
-    if (!c->pd_out) { HIPCHK(c, hipMalloc(&c->pd_out, 16 * sizeof(float))); c->pd_cap = 16; }
-    st = pairdist_run(c, slot, s1, s2, dim, c->pd_out); if (st) return st;
+    if (!c->pd_out.get()) HIPCHK(c, c->pd_out.reserve(16, grbuf::exact));
+    st = pairdist_run(c, slot, s1, s2, dim, c->pd_out.get()); if (st) return st;
     float v = 0.f;
-    HIPCHK(c, hipMemcpy(&v, c->pd_out, sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(&v, c->pd_out.get(), sizeof(float), hipMemcpyDeviceToHost));
     if (out) *out = v;
     return GR_OK;
 } catch (...) { return gr_abi_guard(); }
@@ -1504,25 +1499,18 @@ static int geometry_filter(gr_ctx *c, uint32_t slot, const Group &g, const gr_sh
     const size_t words = ((size_t)g.n + 63) / 64;
     // (the mask buffers live with the context: a hipMalloc / hipFree pair per call cost more than the kernel and the copy together, and the
     //  copy lands in pinned memory)
-    if (words > c->shape_mask_cap) {
-        if (c->shape_mask_dev) (void)hipFree(c->shape_mask_dev);
-        if (c->shape_mask_host) (void)hipHostFree(c->shape_mask_host);
-        c->shape_mask_dev = nullptr; c->shape_mask_host = nullptr; c->shape_mask_cap = 0;
-        const size_t cap = words + words / 8 + 64;
-        HIPCHK(c, hipMalloc(&c->shape_mask_dev, cap * sizeof(unsigned long long)));
-        HIPCHK(c, hipHostMalloc(&c->shape_mask_host, cap * sizeof(unsigned long long), hipHostMallocDefault));
-        c->shape_mask_cap = cap;
-    }
-    unsigned long long *mask_dev = c->shape_mask_dev;
+    HIPCHK(c, c->shape_mask_dev.reserve(words, grbuf::eighth_plus_64));
+    HIPCHK(c, c->shape_mask_host.reserve(words, grbuf::eighth_plus_64));
+    unsigned long long *mask_dev = c->shape_mask_dev.get();
     if (!c->shape_set_dev) HIPCHK(c, hipMalloc(&c->shape_set_dev, sizeof(GrShapeSet)));
     HIPCHK(c, hipMemcpyAsync(c->shape_set_dev, &set, sizeof set, hipMemcpyHostToDevice, c->stream));     // (pageable source: staged by the runtime before the call returns)
     {
         SlotUse use(c, slot);
         k_shape_mask<<<dim3((unsigned)((g.n + 255) / 256)), dim3(256), 0, c->stream>>>(c->frames + (size_t)slot * c->frame_stride, sel, c->boxes_dev + slot, c->shape_set_dev, mask_dev);
     }
-    const unsigned long long *mask = c->shape_mask_host;
+    const unsigned long long *mask = c->shape_mask_host.get();
     hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(c->shape_mask_host, mask_dev, words * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->shape_mask_host.get(), mask_dev, words * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) { c->err = std::string("geometry selection: ") + hipGetErrorString(e); return GR_E_HIP; }
     // ordinal -> atom index in the source group's iteration order (AtomContainer::iter, container.rs:381-411): the set bits of each word
@@ -1679,10 +1667,10 @@ int gr_sel_all_distances(gr_ctx *c, uint32_t slot, const uint64_t *s1, const uin
     TempSel b(c, s2, e2, n2, &st); if (st) return st;
     const size_t total = (size_t)a.g.n * b.g.n;
     if (total > cap || (total && !out_host)) return fail(c, GR_E_INVALID_ARG, "output buffer too small");
-    st = pairdist_reserve(c, total); if (st) return st;
-    st = pairdist_run(c, slot, make_sel(a.g), make_sel(b.g), dim, c->pd_out); if (st) return st;
+    HIPCHK(c, c->pd_out.reserve(total, grbuf::exact));
+    st = pairdist_run(c, slot, make_sel(a.g), make_sel(b.g), dim, c->pd_out.get()); if (st) return st;
     if (total) {
-        HIPCHK(c, hipMemcpyAsync(out_host, c->pd_out, total * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(out_host, c->pd_out.get(), total * sizeof(float), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
     return GR_OK;
@@ -1843,17 +1831,11 @@ static int center_resident(gr_ctx *c, uint32_t s0, uint32_t nb, const GrSel &all
     const uint32_t res_stream = wgs * streams;
     const uint32_t n_fin = std::min<uint32_t>(streams > 8 ? GR_RES_MAX_FIN : 8, c->res_max_wgs - res_stream);
     const size_t rec_words = (size_t)nb * ((wgs + GR_RES_REC_PAD - 1u) & ~(uint32_t)(GR_RES_REC_PAD - 1u)) * GR_RES_REC_WORDS;
-    if (rec_words > c->res_wgrec_cap) {
-        if (c->res_wgrec) (void)hipFree(c->res_wgrec);
-        c->res_wgrec = nullptr; c->res_wgrec_cap = 0;
-        HIPCHK(c, hipMalloc(&c->res_wgrec, rec_words * sizeof(unsigned long long)));
-        HIPCHK(c, hipMemsetAsync(c->res_wgrec, 0, rec_words * sizeof(unsigned long long), S));   // tag 0 = no launch
-        c->res_wgrec_cap = rec_words;
-    }
+    { const int sr = res_wgrec_reserve(c, rec_words, S); if (sr) return sr; }
     GrResCtl ctl;
     memset(&ctl, 0, sizeof ctl);
     { const int se = res_next_epoch(c, &ctl.epoch); if (se) return se; }
-    ctl.wgrec = c->res_wgrec; ctl.rec = c->res_rec; ctl.abort = c->res_abort; ctl.progress = c->res_progress; ctl.n_stream = res_stream; ctl.n_fin = n_fin;
+    ctl.wgrec = c->res_wgrec.get(); ctl.rec = c->res_rec; ctl.abort = c->res_abort; ctl.progress = c->res_progress; ctl.n_stream = res_stream; ctl.n_fin = n_fin;
     ctl.checkin_target = c->res_checkin + res_stream + n_fin; ctl.fresh_states = fresh_states ? 1u : 0u;
     ctl.wgs_frame = wgs; ctl.streams = streams; ctl.groups_wg = gwg;
     ctl.team_waves = resident_team_waves(wgs, streams);
@@ -2286,12 +2268,7 @@ static int segment_begin(gr_rmsd_plan *p, uint32_t s0, uint32_t nb, int fit) {
         if (lite) {
             size_t need = 0;
             for (uint32_t f0 = 0; f0 < nb; f0 += sb) need = std::max(need, (size_t)nb * fit_grid(c, std::min<uint32_t>(sb, nb - f0)) * (GR_WG / 64));   // (one word per wave)
-            if (need > c->fit_partials_cap) {
-                if (c->fit_partials) (void)hipFree(c->fit_partials);
-                c->fit_partials = nullptr; c->fit_partials_cap = 0;
-                HIPCHK(c, hipMalloc(&c->fit_partials, need * sizeof(double)));
-                c->fit_partials_cap = need;
-            }
+            HIPCHK(c, c->fit_partials.reserve(need, grbuf::exact));
         }
         const bool fused = (lite || fast) && c->fuse;   // the finalize rides on the tail of the sums kernel
         q.fused = fused;
@@ -2306,23 +2283,12 @@ static int segment_begin(gr_rmsd_plan *p, uint32_t s0, uint32_t nb, int fit) {
             // ONE launch for the segment: every frame is read once and written once (gr_resident.h)
             const uint32_t res_stream = res_wgs * res_streams;
             const uint32_t n_fin = std::min<uint32_t>(res_streams > 8 ? GR_RES_MAX_FIN : 8, c->res_max_wgs - res_stream);
-            if ((size_t)nb * res_wgs * GrResShape::WAVES > c->fit_partials_cap) {      // (one word per streaming WAVE and frame)
-                if (c->fit_partials) (void)hipFree(c->fit_partials);
-                c->fit_partials = nullptr; c->fit_partials_cap = 0;
-                HIPCHK(c, hipMalloc(&c->fit_partials, (size_t)nb * res_wgs * GrResShape::WAVES * sizeof(double)));
-                c->fit_partials_cap = (size_t)nb * res_wgs * GrResShape::WAVES;
-            }
+            HIPCHK(c, c->fit_partials.reserve((size_t)nb * res_wgs * GrResShape::WAVES, grbuf::exact));      // (one word per streaming WAVE and frame)
             const size_t rec_words = (size_t)nb * ((res_wgs + GR_RES_REC_PAD - 1u) & ~(uint32_t)(GR_RES_REC_PAD - 1u)) * GR_RES_REC_WORDS;
-            if (rec_words > c->res_wgrec_cap) {
-                if (c->res_wgrec) (void)hipFree(c->res_wgrec);
-                c->res_wgrec = nullptr; c->res_wgrec_cap = 0;
-                HIPCHK(c, hipMalloc(&c->res_wgrec, rec_words * sizeof(unsigned long long)));
-                HIPCHK(c, hipMemsetAsync(c->res_wgrec, 0, rec_words * sizeof(unsigned long long), S));   // tag 0 = no launch
-                c->res_wgrec_cap = rec_words;
-            }
+            st = res_wgrec_reserve(c, rec_words, S); if (st) return st;
             GrResCtl ctl;
             st = res_next_epoch(c, &ctl.epoch); if (st) return st;
-            ctl.wgrec = c->res_wgrec; ctl.rec = c->res_rec; ctl.abort = c->res_abort; ctl.progress = c->res_progress; ctl.n_stream = res_stream; ctl.n_fin = n_fin;
+            ctl.wgrec = c->res_wgrec.get(); ctl.rec = c->res_rec; ctl.abort = c->res_abort; ctl.progress = c->res_progress; ctl.n_stream = res_stream; ctl.n_fin = n_fin;
             ctl.checkin_target = c->res_checkin + res_stream + n_fin; ctl.fresh_states = states_unset ? 1u : 0u;
             ctl.wgs_frame = res_wgs; ctl.streams = res_streams; ctl.groups_wg = res_gwg;
             ctl.team_waves = resident_team_waves(res_wgs, res_streams);
@@ -2364,7 +2330,7 @@ static int segment_begin(gr_rmsd_plan *p, uint32_t s0, uint32_t nb, int fit) {
 #endif
             float *frames = c->frames; size_t stride = c->frame_stride; uint32_t slot0 = s0, nfr = nb, natoms = (uint32_t)c->n;
             const float *masses = c->masses; GrSel sel_arg = sel; const GrBox *boxes = c->boxes_dev; GrPlanDev plan = res_msk ? plan_span : p->dev;
-            GrFrameState *states = c->state_dev; double *fparts = c->fit_partials;
+            GrFrameState *states = c->state_dev; double *fparts = c->fit_partials.get();
             void *args[] = { &frames, &stride, &slot0, &nfr, &natoms, &masses, &sel_arg, &boxes, &plan, &states, &fparts, &ctl };
             bool ubox = true;   // the same box in every frame of the segment (constant-volume runs): its constants are loaded once
             for (uint32_t f = 1; f < nb && ubox; ++f) ubox = memcmp(&c->boxes_host[s0 + f], &c->boxes_host[s0], sizeof(GrBox)) == 0;
@@ -2394,7 +2360,7 @@ static int segment_begin(gr_rmsd_plan *p, uint32_t s0, uint32_t nb, int fit) {
                 // memory; segment_end polls its sequence word: no copy, no stream synchronisation
                 q.res_fresh = states_unset; q.res_epoch = ctl.epoch;
                 states_unset = false;
-                st = res_close<0>(c, nb, c->fit_partials, res_wgs * GrResShape::WAVES, p->dev.sw, ctl.epoch, q.res_fresh, &q.res_seq); if (st) return st;
+                st = res_close<0>(c, nb, c->fit_partials.get(), res_wgs * GrResShape::WAVES, p->dev.sw, ctl.epoch, q.res_fresh, &q.res_seq); if (st) return st;
                 q.resident = true; q.res_stream = res_stream; q.res_streams = res_streams;
                 q.rmsd_fast = false;                    // (the pass closes its frames with the fit's own sum: nothing to hand back)
                 c->res_last_streams = res_streams;
@@ -2428,10 +2394,10 @@ static int segment_begin(gr_rmsd_plan *p, uint32_t s0, uint32_t nb, int fit) {
             if (fit) {
                 if (c->profile) EVREC(c, c->pev[6 * g + 4], true, S);
                 // (closing the rmsd on the tail of this kernel makes every one of its 62 k workgroups drain its stores: 3x slower)
-                if (lite) k_fit_pk<true><<<dim3(gx, nf), dim3(GR_WG), stream_lds(c, GR_STREAM_WGS_CU_DEFAULT), S>>>(c->frames, c->frame_stride, s0 + f0, (uint32_t)c->n, c->boxes_dev, p->dev, c->state_dev + f0, c->masses, sel, c->fit_partials + (size_t)f0 * gx * (GR_WG / 64));
+                if (lite) k_fit_pk<true><<<dim3(gx, nf), dim3(GR_WG), stream_lds(c, GR_STREAM_WGS_CU_DEFAULT), S>>>(c->frames, c->frame_stride, s0 + f0, (uint32_t)c->n, c->boxes_dev, p->dev, c->state_dev + f0, c->masses, sel, c->fit_partials.get() + (size_t)f0 * gx * (GR_WG / 64));
                 else k_fit_pk<false><<<dim3(gx, nf), dim3(GR_WG), 0, S>>>(c->frames, c->frame_stride, s0 + f0, (uint32_t)c->n, c->boxes_dev, p->dev, c->state_dev + f0, c->masses, sel, nullptr);
                 if (c->profile) EVREC(c, c->pev[6 * g + 5], true, S);
-                if (lite) k_rmsd_close<<<dim3(nf), dim3(64), 0, S>>>(c->fit_partials + (size_t)f0 * gx * (GR_WG / 64), gx * (GR_WG / 64), p->dev.sw, c->state_dev + f0);
+                if (lite) k_rmsd_close<<<dim3(nf), dim3(64), 0, S>>>(c->fit_partials.get() + (size_t)f0 * gx * (GR_WG / 64), gx * (GR_WG / 64), p->dev.sw, c->state_dev + f0);
             }
         }
         HIPCHK(c, hipGetLastError());
@@ -2851,6 +2817,52 @@ int gr_xtc_read_frame(const gr_xtc *x, uint64_t frame, float *xyz, float box9[9]
     return xtc_status(grx::decode_frame(x->f, x->f.frames[frame], xyz, scratch));
 } catch (...) { return gr_abi_guard(); }
 
+// ---- the device readers' shared ingest path (C5): two staging banks (pinned host + device) that the calls take in turn.  The order below
+// is the contract: a bank's pinned half is reused once its last H2D copy has run (xtc_ev), its device half once its last unpack kernel
+// has (xtc_unpacked); a slot's box is rewritten once its last box copy has run (ev_ready); the unpack stream writes slots and boxes
+// only behind the last kernels that read them (ev_done_ring).
+struct IngestBank { uint32_t bank; unsigned char *H, *D; };
+
+// takes the next bank (it stays taken when the call fails later) with room for `bytes` in both halves
+static int ingest_acquire(gr_ctx *c, size_t bytes, IngestBank *b) {
+    const uint32_t bank = c->xtc_bank; c->xtc_bank ^= 1u;
+    if (c->xtc_ev[bank]) HIPCHK(c, hipEventSynchronize(c->xtc_ev[bank]));       // the batch before the previous one has left this bank
+    else HIPCHK(c, hipEventCreateWithFlags(&c->xtc_ev[bank], hipEventDisableTiming));
+    HIPCHK(c, c->xtc_host[bank].reserve(bytes, grbuf::quarter));
+    if (!c->unpack_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->unpack_stream, hipStreamNonBlocking));
+    if (!c->xtc_unpacked[bank]) HIPCHK(c, hipEventCreateWithFlags(&c->xtc_unpacked[bank], hipEventDisableTiming));
+    if (bytes > c->xtc_dev[bank].cap()) HIPCHK(c, hipStreamSynchronize(c->unpack_stream));        // nobody reads the old bank any more
+    HIPCHK(c, c->xtc_dev[bank].reserve(bytes, grbuf::quarter));
+    *b = { bank, c->xtc_host[bank].get(), c->xtc_dev[bank].get() };
+    return GR_OK;
+}
+// copy stream: copy() -- the bank's H2D -- once the unpack kernel that last read the device bank is done.  unpack stream: behind that
+// copy and behind the last kernels that still read these slots -- the boxes (one copy from the pinned boxes_host range: every
+// box_fill of the call comes before), launch() -- the unpack kernel -- then the slots' ready events.  Both return a status.
+extern "C++" {      // (a template, inside the C ABI's block)
+template <class Copy, class Launch>
+static int ingest_submit(gr_ctx *c, uint32_t bank, uint32_t first_slot, uint32_t n_frames, Copy copy, Launch launch) {
+    HIPCHK(c, hipStreamWaitEvent(c->copy_stream, c->xtc_unpacked[bank], 0));
+    int st = copy(c->copy_stream); if (st) return st;
+    HIPCHK(c, hipEventRecord(c->xtc_ev[bank], c->copy_stream));
+    hipStream_t U = c->unpack_stream;
+    HIPCHK(c, hipStreamWaitEvent(U, c->xtc_ev[bank], 0));
+    uint64_t waited = 0;
+    for (uint32_t k = 0; k < n_frames; ++k) {
+        const uint64_t gen = c->slot_gen[first_slot + k];
+        if (gen && gen != waited) { HIPCHK(c, hipStreamWaitEvent(U, c->ev_done_ring[gen % 64], 0)); waited = gen; }
+    }
+    HIPCHK(c, hipMemcpyAsync(c->boxes_dev + first_slot, c->boxes_host + first_slot, (size_t)n_frames * sizeof(GrBox), hipMemcpyHostToDevice, U));
+    st = launch(U); if (st) return st;
+    HIPCHK(c, hipEventRecord(c->xtc_unpacked[bank], U));
+    for (uint32_t k = 0; k < n_frames; ++k) {
+        HIPCHK(c, hipEventRecord(c->ev_ready[first_slot + k], U));
+        c->upload_pending[first_slot + k] = 1;
+    }
+    return GR_OK;
+}
+}
+
 // frames of an xtc file -> frame slots, unpacked on the device.  group == nullptr: every atom (XtcReader); else only the atoms of
 // the group change (GroupXtcReader, molly_xtc.rs:440-470,585-587): the host reads + skims the bit stream only up to the group's
 // last atom, only that prefix crosses PCIe, and the unpack kernel writes the group's atoms only.
@@ -2907,27 +2919,9 @@ static int xtc_read_frames_device_impl(const gr_xtc *x, uint64_t first_frame, ui
     const size_t off_desc = bytes;  bytes += (size_t)n_frames * sizeof(grx::FrameDesc);
     const size_t off_slot = bytes;  bytes += (((size_t)n_frames * sizeof(uint32_t)) + 15) & ~(size_t)15;
     const size_t off_cp = bytes;    bytes += (size_t)n_frames * (ncp ? ncp : 1) * sizeof(grx::Checkpoint);
-    const uint32_t bank = c->xtc_bank; c->xtc_bank ^= 1u;
-    if (c->xtc_ev[bank]) HIPCHK(c, hipEventSynchronize(c->xtc_ev[bank]));       // the batch before the previous one has left this bank
-    else HIPCHK(c, hipEventCreateWithFlags(&c->xtc_ev[bank], hipEventDisableTiming));
-    if (bytes > c->xtc_host_cap[bank]) {
-        if (c->xtc_host[bank]) (void)hipHostFree(c->xtc_host[bank]);
-        c->xtc_host[bank] = nullptr; c->xtc_host_cap[bank] = 0;
-        const size_t cap = bytes + bytes / 4;
-        HIPCHK(c, hipHostMalloc(&c->xtc_host[bank], cap, hipHostMallocDefault));
-        c->xtc_host_cap[bank] = cap;
-    }
-    if (!c->unpack_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->unpack_stream, hipStreamNonBlocking));
-    if (!c->xtc_unpacked[bank]) HIPCHK(c, hipEventCreateWithFlags(&c->xtc_unpacked[bank], hipEventDisableTiming));
-    if (bytes > c->xtc_dev_cap[bank]) {
-        HIPCHK(c, hipStreamSynchronize(c->unpack_stream));        // nobody reads the old bank any more
-        if (c->xtc_dev[bank]) (void)hipFree(c->xtc_dev[bank]);
-        c->xtc_dev[bank] = nullptr; c->xtc_dev_cap[bank] = 0;
-        const size_t cap = bytes + bytes / 4;
-        HIPCHK(c, hipMalloc(&c->xtc_dev[bank], cap));
-        c->xtc_dev_cap[bank] = cap;
-    }
-    unsigned char *H = c->xtc_host[bank];
+    IngestBank ib;
+    st = ingest_acquire(c, bytes, &ib); if (st) return st;
+    unsigned char *const H = ib.H, *const D = ib.D;
     grx::FrameDesc *descs = reinterpret_cast<grx::FrameDesc *>(H + off_desc);
     uint32_t *slots = reinterpret_cast<uint32_t *>(H + off_slot);
     grx::Checkpoint *cps = reinterpret_cast<grx::Checkpoint *>(H + off_cp);
@@ -2966,29 +2960,13 @@ static int xtc_read_frames_device_impl(const gr_xtc *x, uint64_t first_frame, ui
             }
         }
     };
-    uint32_t nt = host_threads > 0 ? (uint32_t)host_threads : std::min<uint32_t>(n_frames, 16u);
-    nt = std::max<uint32_t>(1u, std::min<uint32_t>(nt, n_frames));
+    const uint32_t nt = grw::worker_count(host_threads, n_frames);
     if (nt == 1) work();
-    else {
-        // (a thread that cannot be started must not unwind through the C ABI: the frames it would have taken are picked up by
-        // the workers that did start, or by this thread)
-        std::vector<std::thread> th;
-        for (uint32_t t = 0; t < nt; ++t) { try { th.emplace_back(work); } catch (const std::system_error &) { break; } }
-        if (th.empty()) work();
-        for (auto &t : th) t.join();
-    }
+    else for (auto &t : grw::start_workers(nt, work)) t.join();
     if (bad.load() != grx::XTC_OK) return fail(c, xtc_status(bad.load()), "corrupt or unreadable xtc frame");
     const auto t_host = std::chrono::steady_clock::now();
-    // ---- device.  copy stream: the bank's H2D, once the unpack kernel that last read the device bank is done.
-    // unpack stream: behind that copy and behind the last kernels that still read these slots -- the boxes (one copy from
-    // the pinned boxes_host range), the unpack kernel, then the slots' ready events.
-    unsigned char *D = c->xtc_dev[bank];
-    for (uint32_t k = 0; k < n_frames; ++k) {
-        const uint32_t slot = first_slot + k;
-        // boxes_host[slot] is about to be rewritten: the slot's previous box copy must have left it (see gr_frame_upload)
-        if (c->ev_ready[slot]) HIPCHK(c, hipEventSynchronize(c->ev_ready[slot]));
-        else HIPCHK(c, hipEventCreateWithFlags(&c->ev_ready[slot], hipEventDisableTiming));
-    }
+    // ---- device (ingest_submit)
+    for (uint32_t k = 0; k < n_frames; ++k) { st = slot_box_wait(c, first_slot + k); if (st) return st; }
     for (uint32_t k = 0; k < n_frames; ++k) {
         const uint64_t fr = first_frame + k * frame_step;
         float box9[9];
@@ -2996,35 +2974,25 @@ static int xtc_read_frames_device_impl(const gr_xtc *x, uint64_t first_frame, ui
         if (st != GR_OK) return fail(c, st, "unsupported box in xtc frame", fr);
         box_fill(c, first_slot + k, box9);
     }
-    HIPCHK(c, hipStreamWaitEvent(c->copy_stream, c->xtc_unpacked[bank], 0));
-    if (n_stop >= n) {
-        HIPCHK(c, hipMemcpyAsync(D, H, bytes, hipMemcpyHostToDevice, c->copy_stream));
-    } else {
-        // partial read: only the stream prefixes the skim said the group needs cross PCIe, then the tables
-        for (uint32_t k = 0; k < n_frames; ++k)
-            if (descs[k].nbytes) HIPCHK(c, hipMemcpyAsync(D + soff[k], H + soff[k], ((size_t)descs[k].nbytes + 16 + 15) & ~(size_t)15, hipMemcpyHostToDevice, c->copy_stream));
-        HIPCHK(c, hipMemcpyAsync(D + stream_bytes, H + stream_bytes, bytes - stream_bytes, hipMemcpyHostToDevice, c->copy_stream));
-    }
-    HIPCHK(c, hipEventRecord(c->xtc_ev[bank], c->copy_stream));
-    hipStream_t U = c->unpack_stream;
-    HIPCHK(c, hipStreamWaitEvent(U, c->xtc_ev[bank], 0));
-    uint64_t waited = 0;
-    for (uint32_t k = 0; k < n_frames; ++k) {
-        const uint64_t gen = c->slot_gen[first_slot + k];
-        if (gen && gen != waited) { HIPCHK(c, hipStreamWaitEvent(U, c->ev_done_ring[gen % 64], 0)); waited = gen; }
-    }
-    HIPCHK(c, hipMemcpyAsync(c->boxes_dev + first_slot, c->boxes_host + first_slot, (size_t)n_frames * sizeof(GrBox), hipMemcpyHostToDevice, U));
-    if (ncp) {
+    st = ingest_submit(c, ib.bank, first_slot, n_frames, [&](hipStream_t S) -> int {
+        if (n_stop >= n) {
+            HIPCHK(c, hipMemcpyAsync(D, H, bytes, hipMemcpyHostToDevice, S));
+        } else {
+            // partial read: only the stream prefixes the skim said the group needs cross PCIe, then the tables
+            for (uint32_t k = 0; k < n_frames; ++k)
+                if (descs[k].nbytes) HIPCHK(c, hipMemcpyAsync(D + soff[k], H + soff[k], ((size_t)descs[k].nbytes + 16 + 15) & ~(size_t)15, hipMemcpyHostToDevice, S));
+            HIPCHK(c, hipMemcpyAsync(D + stream_bytes, H + stream_bytes, bytes - stream_bytes, hipMemcpyHostToDevice, S));
+        }
+        return GR_OK;
+    }, [&](hipStream_t U) -> int {
+        if (!ncp) return GR_OK;
         k_xtc_unpack<<<dim3((ncp + 255) / 256, n_frames), dim3(256), 0, U>>>(
             D, reinterpret_cast<const grx::FrameDesc *>(D + off_desc), reinterpret_cast<const grx::Checkpoint *>(D + off_cp),
             c->frames, c->frame_stride, reinterpret_cast<const uint32_t *>(D + off_slot), n, g ? g->mask_dev : nullptr);
         HIPCHK(c, hipGetLastError());
-    }
-    HIPCHK(c, hipEventRecord(c->xtc_unpacked[bank], U));
-    for (uint32_t k = 0; k < n_frames; ++k) {
-        HIPCHK(c, hipEventRecord(c->ev_ready[first_slot + k], U));
-        c->upload_pending[first_slot + k] = 1;
-    }
+        return GR_OK;
+    });
+    if (st) return st;
     if (trace) {
         const auto t_end = std::chrono::steady_clock::now();
         auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
@@ -3160,25 +3128,9 @@ int gr_trr_read_frames_device(const gr_trr *t, uint64_t first_frame, uint32_t n_
     const size_t off_sec = bytes;  bytes += (size_t)n_frames * sizeof(uint64_t);
     const size_t off_rs = bytes;   bytes += (((size_t)n_frames * sizeof(uint32_t)) + 15) & ~(size_t)15;
     const size_t off_slot = bytes; bytes += (((size_t)n_frames * sizeof(uint32_t)) + 15) & ~(size_t)15;
-    const uint32_t bank = c->xtc_bank; c->xtc_bank ^= 1u;
-    if (c->xtc_ev[bank]) HIPCHK(c, hipEventSynchronize(c->xtc_ev[bank]));
-    else HIPCHK(c, hipEventCreateWithFlags(&c->xtc_ev[bank], hipEventDisableTiming));
-    if (bytes > c->xtc_host_cap[bank]) {
-        if (c->xtc_host[bank]) (void)hipHostFree(c->xtc_host[bank]);
-        c->xtc_host[bank] = nullptr; c->xtc_host_cap[bank] = 0;
-        HIPCHK(c, hipHostMalloc(&c->xtc_host[bank], bytes + bytes / 4, hipHostMallocDefault));
-        c->xtc_host_cap[bank] = bytes + bytes / 4;
-    }
-    if (!c->unpack_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->unpack_stream, hipStreamNonBlocking));
-    if (!c->xtc_unpacked[bank]) HIPCHK(c, hipEventCreateWithFlags(&c->xtc_unpacked[bank], hipEventDisableTiming));
-    if (bytes > c->xtc_dev_cap[bank]) {
-        HIPCHK(c, hipStreamSynchronize(c->unpack_stream));
-        if (c->xtc_dev[bank]) (void)hipFree(c->xtc_dev[bank]);
-        c->xtc_dev[bank] = nullptr; c->xtc_dev_cap[bank] = 0;
-        HIPCHK(c, hipMalloc(&c->xtc_dev[bank], bytes + bytes / 4));
-        c->xtc_dev_cap[bank] = bytes + bytes / 4;
-    }
-    unsigned char *H = c->xtc_host[bank], *D = c->xtc_dev[bank];
+    IngestBank ib;
+    st = ingest_acquire(c, bytes, &ib); if (st) return st;
+    unsigned char *const H = ib.H, *const D = ib.D;
     uint64_t *sec = reinterpret_cast<uint64_t *>(H + off_sec);
     uint32_t *rsz = reinterpret_cast<uint32_t *>(H + off_rs), *slots = reinterpret_cast<uint32_t *>(H + off_slot);
     for (uint32_t k = 0; k < n_frames; ++k) {
@@ -3190,33 +3142,21 @@ int gr_trr_read_frames_device(const gr_trr *t, uint64_t first_frame, uint32_t n_
             sec[k] = soff[k];
         } else sec[k] = ~0ull;
         rsz[k] = fi.real_size; slots[k] = slot;
-        if (c->ev_ready[slot]) HIPCHK(c, hipEventSynchronize(c->ev_ready[slot]));
-        else HIPCHK(c, hipEventCreateWithFlags(&c->ev_ready[slot], hipEventDisableTiming));
+        st = slot_box_wait(c, slot); if (st) return st;
         float box9[9];
         st = gr_trr_frame_info(t, fr, steps ? steps + k : nullptr, times ? times + k : nullptr, nullptr, box9, nullptr, nullptr);
         if (st != GR_OK) return fail(c, st, "unsupported box in trr frame", fr);
         box_fill(c, slot, fi.has_box ? box9 : nullptr);
     }
-    HIPCHK(c, hipStreamWaitEvent(c->copy_stream, c->xtc_unpacked[bank], 0));
-    HIPCHK(c, hipMemcpyAsync(D, H, bytes, hipMemcpyHostToDevice, c->copy_stream));
-    HIPCHK(c, hipEventRecord(c->xtc_ev[bank], c->copy_stream));
-    hipStream_t U = c->unpack_stream;
-    HIPCHK(c, hipStreamWaitEvent(U, c->xtc_ev[bank], 0));
-    uint64_t waited = 0;
-    for (uint32_t k = 0; k < n_frames; ++k) {
-        const uint64_t gen = c->slot_gen[first_slot + k];
-        if (gen && gen != waited) { HIPCHK(c, hipStreamWaitEvent(U, c->ev_done_ring[gen % 64], 0)); waited = gen; }
-    }
-    HIPCHK(c, hipMemcpyAsync(c->boxes_dev + first_slot, c->boxes_host + first_slot, (size_t)n_frames * sizeof(GrBox), hipMemcpyHostToDevice, U));
-    k_trr_unpack<<<dim3((t->f.natoms + 255) / 256, n_frames), dim3(256), 0, U>>>(D, reinterpret_cast<const uint64_t *>(D + off_sec), reinterpret_cast<const uint32_t *>(D + off_rs),
-                                                                                  c->frames, c->frame_stride, reinterpret_cast<const uint32_t *>(D + off_slot), t->f.natoms);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->xtc_unpacked[bank], U));
-    for (uint32_t k = 0; k < n_frames; ++k) {
-        HIPCHK(c, hipEventRecord(c->ev_ready[first_slot + k], U));
-        c->upload_pending[first_slot + k] = 1;
-    }
-    return GR_OK;
+    return ingest_submit(c, ib.bank, first_slot, n_frames, [&](hipStream_t S) -> int {
+        HIPCHK(c, hipMemcpyAsync(D, H, bytes, hipMemcpyHostToDevice, S));
+        return GR_OK;
+    }, [&](hipStream_t U) -> int {
+        k_trr_unpack<<<dim3((t->f.natoms + 255) / 256, n_frames), dim3(256), 0, U>>>(D, reinterpret_cast<const uint64_t *>(D + off_sec), reinterpret_cast<const uint32_t *>(D + off_rs),
+                                                                                      c->frames, c->frame_stride, reinterpret_cast<const uint32_t *>(D + off_slot), t->f.natoms);
+        HIPCHK(c, hipGetLastError());
+        return GR_OK;
+    });
 } catch (...) { return gr_abi_guard(); }
 
 /* ------------------------------------------------------------ text front end */
@@ -3331,14 +3271,6 @@ int gr_xtc_write_frame(gr_xtc_writer *w, uint64_t n, const float *xyz, const flo
     return fwrite(out.data(), 1, out.size(), w->fp) == out.size() ? GR_OK : GR_E_IO;
 } catch (...) { return gr_abi_guard(); }
 // gr_xtc_write_slots on the device encoder: rounds of frames whose scratch (30 bytes per atom and frame) stays below ~4 GB
-static int xe_reserve(gr_ctx *c, int k, size_t bytes) {
-    if (bytes <= c->xe_cap[k]) return GR_OK;
-    if (c->xe_dev[k]) (void)hipFree(c->xe_dev[k]);
-    c->xe_dev[k] = nullptr; c->xe_cap[k] = 0;
-    HIPCHK(c, hipMalloc(&c->xe_dev[k], bytes));
-    c->xe_cap[k] = bytes;
-    return GR_OK;
-}
 // *declined: the scratch buffers could not be had (nothing has been written): the caller takes the host encoders
 static int xtc_write_slots_device(gr_xtc_writer *w, gr_ctx *c, uint32_t first_slot, uint32_t n_frames, const Group *g,
                                   const int64_t *steps, const float *times, float precision, bool *declined) {
@@ -3355,13 +3287,11 @@ static int xtc_write_slots_device(gr_xtc_writer *w, gr_ctx *c, uint32_t first_sl
     uint32_t round = (uint32_t)std::max<size_t>(1, std::min<size_t>(n_frames, ((size_t)2 << 30) / per_frame));
     round = std::min<uint32_t>(round, (uint32_t)std::max<size_t>(8, ((size_t)64 << 20) / ((size_t)n * 4u)));
     round = std::min<uint32_t>(round, 65535u);      // (a round's frames are the y dimension of the kernels' grids: a small group written from very many slots)
-    int st;
-    if ((st = xe_reserve(c, 0, (size_t)round * n * 12u)) || (st = xe_reserve(c, 1, (size_t)round * n * 8u)) || (st = xe_reserve(c, 2, (size_t)round * n * 8u)) ||
-        (st = xe_reserve(c, 3, (size_t)round * n * 2u + 16u)) || (st = xe_reserve(c, 4, (size_t)round * (sizeof(GrXencHdr) + 8u)))) {
-        (void)hipGetLastError(); *declined = true; return GR_OK;
-    }
-    int *ints = (int *)c->xe_dev[0]; unsigned long long *enc = (unsigned long long *)c->xe_dev[1]; GrXencRun *runs = (GrXencRun *)c->xe_dev[2]; uint16_t *meta = (uint16_t *)c->xe_dev[3];
-    GrXencHdr *hdr_dev = (GrXencHdr *)c->xe_dev[4]; unsigned long long *off_dev = (unsigned long long *)((unsigned char *)c->xe_dev[4] + (size_t)round * sizeof(GrXencHdr));
+    const size_t xe_bytes[5] = { (size_t)round * n * 12u, (size_t)round * n * 8u, (size_t)round * n * 8u, (size_t)round * n * 2u + 16u, (size_t)round * (sizeof(GrXencHdr) + 8u) };
+    auto scratch = [&]() -> int { for (int k = 0; k < 5; ++k) HIPCHK(c, c->xe_dev[k].reserve(xe_bytes[k], grbuf::exact)); return GR_OK; };
+    if (scratch()) { (void)hipGetLastError(); *declined = true; return GR_OK; }
+    int *ints = (int *)c->xe_dev[0].get(); unsigned long long *enc = (unsigned long long *)c->xe_dev[1].get(); GrXencRun *runs = (GrXencRun *)c->xe_dev[2].get(); uint16_t *meta = (uint16_t *)c->xe_dev[3].get();
+    GrXencHdr *hdr_dev = (GrXencHdr *)c->xe_dev[4].get(); unsigned long long *off_dev = (unsigned long long *)(c->xe_dev[4].get() + (size_t)round * sizeof(GrXencHdr));
     const size_t head_bytes = (size_t)round * (sizeof(GrXencHdr) + 8u);
     std::thread writer;                 // the round before this one, on its way into the file
     std::atomic<int> io_err(0);
@@ -3371,17 +3301,9 @@ static int xtc_write_slots_device(gr_xtc_writer *w, gr_ctx *c, uint32_t first_sl
         const uint32_t nf = std::min<uint32_t>(round, n_frames - r0), s0 = first_slot + r0, bank = ri & 1u;
         SlotUse use(c, s0, nf);
         // (bank `bank` was last used by round ri - 2, whose writer was joined before round ri - 1's was started)
-        auto bank_reserve = [&](size_t bytes, bool keep_head) -> int {
-            if (bytes <= c->xe_host_cap[bank]) return GR_OK;
-            unsigned char *bigger = nullptr;
-            HIPCHK(c, hipHostMalloc(&bigger, bytes, hipHostMallocDefault));
-            if (keep_head && c->xe_host[bank]) memcpy(bigger, c->xe_host[bank], head_bytes);
-            if (c->xe_host[bank]) (void)hipHostFree(c->xe_host[bank]);
-            c->xe_host[bank] = bigger; c->xe_host_cap[bank] = bytes;
-            return GR_OK;
-        };
-        if ((st = bank_reserve(head_bytes + (size_t)nf * n * 4u, false))) return st;      // (~4 B per atom: the usual stream; grown below when a round needs more)
-        GrXencHdr *hdr = (GrXencHdr *)c->xe_host[bank]; unsigned long long *off = (unsigned long long *)(c->xe_host[bank] + (size_t)round * sizeof(GrXencHdr));
+        grbuf::Pinned<unsigned char> &xh = c->xe_host[bank];
+        HIPCHK(c, xh.reserve(head_bytes + (size_t)nf * n * 4u, grbuf::exact));      // (~4 B per atom: the usual stream; grown below when a round needs more)
+        GrXencHdr *hdr = (GrXencHdr *)xh.get(); unsigned long long *off = (unsigned long long *)(xh.get() + (size_t)round * sizeof(GrXencHdr));
         for (uint32_t f = 0; f < nf; ++f) { GrXencHdr h = {}; for (int a = 0; a < 3; ++a) { h.mn[a] = INT_MAX; h.mx[a] = INT_MIN; } h.mindiff = (uint32_t)INT_MAX; hdr[f] = h; }
         HIPCHK(c, hipMemcpyAsync(hdr_dev, hdr, (size_t)nf * sizeof(GrXencHdr), hipMemcpyHostToDevice, c->stream));
         k_xenc_quant<<<dim3(std::min<uint32_t>((n + 255u) / 256u, 2048u), nf), dim3(256), 0, c->stream>>>(c->frames, c->frame_stride, s0, sel, n, precision, ints, hdr_dev);
@@ -3404,15 +3326,15 @@ static int xtc_write_slots_device(gr_xtc_writer *w, gr_ctx *c, uint32_t first_sl
             max_runs = std::max(max_runs, h.n_runs);
         }
         if (n_good) {
-            if ((st = xe_reserve(c, 5, (size_t)total))) return st;
-            unsigned char *out_dev = (unsigned char *)c->xe_dev[5];
-            if ((st = bank_reserve(head_bytes + (size_t)total, true))) return st;
-            hdr = (GrXencHdr *)c->xe_host[bank]; off = (unsigned long long *)(c->xe_host[bank] + (size_t)round * sizeof(GrXencHdr));
+            HIPCHK(c, c->xe_dev[5].reserve((size_t)total, grbuf::exact));
+            unsigned char *out_dev = c->xe_dev[5].get();
+            HIPCHK(c, xh.reserve_keep(head_bytes + (size_t)total, grbuf::exact, head_bytes));      // (the headers and offsets above stay)
+            hdr = (GrXencHdr *)xh.get(); off = (unsigned long long *)(xh.get() + (size_t)round * sizeof(GrXencHdr));
             HIPCHK(c, hipMemsetAsync(out_dev, 0, (size_t)total, c->stream));
             HIPCHK(c, hipMemcpyAsync(off_dev, off, (size_t)n_good * 8u, hipMemcpyHostToDevice, c->stream));
             k_xenc_emit<<<dim3(std::max<uint32_t>(1u, std::min<uint32_t>((max_runs + 255u) / 256u, 4096u)), n_good), dim3(256), 0, c->stream>>>(ints, n, hdr_dev, runs, meta, off_dev, out_dev);
             HIPCHK(c, hipGetLastError());
-            unsigned char *streams = c->xe_host[bank] + head_bytes;
+            unsigned char *streams = xh.get() + head_bytes;
             HIPCHK(c, hipMemcpyAsync(streams, out_dev, (size_t)total, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
             // the frames' 92-byte headers, then the round goes to the writer (behind the round before it: the file is written in order)
@@ -3480,13 +3402,8 @@ int gr_xtc_write_slots(gr_xtc_writer *w, gr_ctx *c, uint32_t first_slot, uint32_
     const size_t fb = (size_t)c->n * 3 * sizeof(float);
     // D2H of the whole batch on the compute stream into one pinned buffer (frames are ordered behind the kernels that wrote them);
     // per-frame events let the encoders start as soon as their frame has landed
-    if (fb * n_frames > c->wr_cap) {
-        if (c->wr_host) (void)hipHostFree(c->wr_host);
-        c->wr_host = nullptr; c->wr_cap = 0;
-        HIPCHK(c, hipHostMalloc(&c->wr_host, fb * n_frames, hipHostMallocDefault));
-        c->wr_cap = fb * n_frames;
-    }
-    float *host = c->wr_host;
+    HIPCHK(c, c->wr_host.reserve((size_t)c->n * 3 * n_frames, grbuf::exact));
+    float *host = c->wr_host.get();
     std::vector<hipEvent_t> ev(n_frames, nullptr);
     {
         SlotUse use(c, first_slot, n_frames);
@@ -3526,11 +3443,7 @@ int gr_xtc_write_slots(gr_xtc_writer *w, gr_ctx *c, uint32_t first_slot, uint32_
             done[k].store(ok ? 1 : 2);
         }
     };
-    uint32_t nt = host_threads > 0 ? (uint32_t)host_threads : std::min<uint32_t>(n_frames, 16u);
-    nt = std::max<uint32_t>(1u, std::min<uint32_t>(nt, n_frames));
-    std::vector<std::thread> th;
-    for (uint32_t t = 0; t < nt; ++t) { try { th.emplace_back(work); } catch (const std::system_error &) { break; } }
-    if (th.empty()) work();   // no worker could be started: encode here, then write
+    std::vector<std::thread> th = grw::start_workers(grw::worker_count(host_threads, n_frames), work);   // (none could be started: encoded here, then written)
     int result = GR_OK; uint32_t failed_at = 0;
     for (uint32_t k = 0; k < n_frames && result == GR_OK; ++k) {
         int d;

@@ -219,9 +219,9 @@ struct gr_hbond_plan {
     uint32_t *acc_atom_d = nullptr, *acc_chain_d = nullptr, *hyd_d = nullptr, *pair_lane_d = nullptr;
     GrHbLane *lanes_d = nullptr;
     // workspace, grown on first use: device, pinned host, bond outputs
-    unsigned char *ws = nullptr; size_t ws_cap = 0;
-    unsigned char *hbuf = nullptr; size_t hbuf_cap = 0;
-    unsigned char *outs = nullptr; size_t outs_cap = 0;   // bonds: [5][cap] words
+    grbuf::Dev<unsigned char> ws;
+    grbuf::Pinned<unsigned char> hbuf;
+    grbuf::Dev<unsigned char> outs;   // bonds: [5][cap] words
 };
 
 namespace {
@@ -255,17 +255,6 @@ std::vector<uint32_t> hb_group_atoms(const Group &g) {
 
 size_t hb_al(size_t v) { return (v + 255) & ~(size_t)255; }
 
-int hb_grow(gr_ctx *c, unsigned char *&p, size_t &cap, size_t need, bool pinned) {
-    if (need <= cap) return GR_OK;
-    if (p) { if (pinned) (void)hipHostFree(p); else (void)hipFree(p); }
-    p = nullptr; cap = 0;
-    need = hb_al(need + need / 4);
-    if (pinned) HIPCHK(c, hipHostMalloc((void **)&p, need, hipHostMallocDefault));
-    else HIPCHK(c, hipMalloc((void **)&p, need));
-    cap = need;
-    return GR_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -274,10 +263,7 @@ void gr_hbond_plan_destroy(gr_hbond_plan *p) try {
     if (!p) return;
     if (p->c) { (void)hipSetDevice(p->c->device); (void)hipStreamSynchronize(p->c->stream); }
     if (p->tab) (void)hipFree(p->tab);
-    if (p->ws) (void)hipFree(p->ws);
-    if (p->outs) (void)hipFree(p->outs);
-    if (p->hbuf) (void)hipHostFree(p->hbuf);
-    delete p;
+    delete p;      // (frees the workspace, gr_buf.h)
 } catch (...) {}
 
 gr_hbond_plan *gr_hbond_plan_create(gr_ctx *c, const char *const *groups, uint32_t n_chains, const uint32_t *pairs, uint32_t n_pairs,
@@ -413,16 +399,16 @@ int gr_hbond_batch(gr_hbond_plan *p, uint32_t first_slot, uint32_t n_frames, uin
                  o_rb = o_off + hb_al(8 * (n_t + 1)), o_dbad = o_rb + hb_al(8 * n_rb), o_abad = o_dbad + 8 * (size_t)nf, o_tmp = o_abad + hb_al(4 * (size_t)nf),
                  ws_bytes = o_tmp + hb_al(std::max(tmp_cells, tmp_lanes));
     const size_t rb_bytes = o_tmp - o_rb;                                           // offsets + error words: one read-back
-    st = hb_grow(c, p->ws, p->ws_cap, ws_bytes, false); if (st) return st;
-    st = hb_grow(c, p->hbuf, p->hbuf_cap, hb_al(sizeof(GrHbFrame) * nf) + rb_bytes, true); if (st) return st;
-    unsigned char *W = p->ws;
+    HIPCHK(c, p->ws.reserve(ws_bytes, grbuf::quarter_aligned256));
+    HIPCHK(c, p->hbuf.reserve(hb_al(sizeof(GrHbFrame) * nf) + rb_bytes, grbuf::quarter_aligned256));
+    unsigned char *W = p->ws.get();
     GrHbFrame *fr_d = (GrHbFrame *)(W + o_fr);
     uint32_t *cell_count = (uint32_t *)(W + o_cc), *cell_start = (uint32_t *)(W + o_cs), *keys = (uint32_t *)(W + o_key), *ranks = (uint32_t *)(W + o_rank),
              *counts = (uint32_t *)(W + o_cnt), *acc_bad = (uint32_t *)(W + o_abad);
     float4 *sorted = (float4 *)(W + o_sort);
     unsigned long long *offs = (unsigned long long *)(W + o_off), *rb = (unsigned long long *)(W + o_rb), *don_bad = (unsigned long long *)(W + o_dbad);
-    GrHbFrame *fr_h = (GrHbFrame *)p->hbuf;
-    unsigned char *rb_h = p->hbuf + hb_al(sizeof(GrHbFrame) * nf);
+    GrHbFrame *fr_h = (GrHbFrame *)p->hbuf.get();
+    unsigned char *rb_h = p->hbuf.get() + hb_al(sizeof(GrHbFrame) * nf);
     memcpy(fr_h, frs.data(), sizeof(GrHbFrame) * nf);
     const float *xyz = c->frames;
     const size_t stride = c->frame_stride;
@@ -461,9 +447,9 @@ int gr_hbond_batch(gr_hbond_plan *p, uint32_t first_slot, uint32_t n_frames, uin
     memcpy(offsets, rb_offs, 8 * n_rb);
     if (n_total) *n_total = total;
     if (total > 0 && total <= max_bonds && donor && hydrogen && acceptor && distance && angle) {
-        st = hb_grow(c, p->outs, p->outs_cap, 20 * (size_t)total, false); if (st) return st;
-        const size_t cap = p->outs_cap / 20;
-        uint32_t *o_don = (uint32_t *)p->outs, *o_h = o_don + cap, *o_acc = o_h + cap;
+        HIPCHK(c, p->outs.reserve(20 * (size_t)total, grbuf::quarter_aligned256));
+        const size_t cap = p->outs.cap() / 20;
+        uint32_t *o_don = (uint32_t *)p->outs.get(), *o_h = o_don + cap, *o_acc = o_h + cap;
         float *o_d = (float *)(o_acc + cap), *o_ang = o_d + cap;
         k_hb_walk<true><<<blocks(n_t), dim3(256), 0, c->stream>>>(xyz, stride, s0, boxes, fr_d, p->lanes_d, p->hyd_d, nl, n_t, cell_start, sorted, p->cutoff,
                                                                    p->min_angle, counts, offs, don_bad, o_don, o_h, o_acc, o_d, o_ang);

@@ -32,7 +32,7 @@ struct GrWhole {
     uint64_t dev_version = ~0ull;       // topology version of the device map
     int32_t *map_dev = nullptr;         // [n_pad]
     uint32_t *rank_dev = nullptr;       // [n_pad] breadth-first rank in the molecule (read only for atoms without position)
-    uint32_t *far_dev = nullptr; uint64_t n_far = 0, far_cap = 0;   // GR_TOPO_FARREF atoms
+    grbuf::Dev<uint32_t> far_dev; uint64_t n_far = 0;   // GR_TOPO_FARREF atoms
     unsigned long long *words_dev = nullptr, *words_host = nullptr; // [GR_MAX_BATCH] frame words (device, pinned)
     explicit GrWhole(uint64_t n) : topo(n) {}
 };
@@ -181,15 +181,10 @@ int whole_upload(gr_ctx *c, GrWhole &W) {
         HIPCHK(c, hipMalloc(&W.words_dev, GR_MAX_BATCH * sizeof(unsigned long long)));
         HIPCHK(c, hipHostMalloc(reinterpret_cast<void **>(&W.words_host), GR_MAX_BATCH * sizeof(unsigned long long), hipHostMallocDefault));
     }
-    if (far.size() > W.far_cap) {
-        if (W.far_dev) (void)hipFree(W.far_dev);
-        W.far_dev = nullptr; W.far_cap = 0;
-        HIPCHK(c, hipMalloc(&W.far_dev, far.size() * sizeof(uint32_t)));
-        W.far_cap = far.size();
-    }
+    HIPCHK(c, W.far_dev.reserve(far.size(), grbuf::exact));
     HIPCHK(c, hipMemcpy(W.map_dev, map.data(), c->n_pad * sizeof(int32_t), hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(W.rank_dev, rank.data(), c->n_pad * sizeof(uint32_t), hipMemcpyHostToDevice));
-    if (!far.empty()) HIPCHK(c, hipMemcpy(W.far_dev, far.data(), far.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (!far.empty()) HIPCHK(c, hipMemcpy(W.far_dev.get(), far.data(), far.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     W.n_far = far.size();
     W.dev_version = W.topo.version;
     return GR_OK;
@@ -230,7 +225,7 @@ int molecules_whole_batch(gr_ctx *c, uint32_t first_slot, uint32_t n_frames, int
                 k_whole_check<<<dim3(check_wgs, k), dim3(256), 0, c->stream>>>(c->frames, c->frame_stride, s0 + a, n_groups, W.map_dev, W.rank_dev, W.words_dev + a);
                 k_whole_place<<<dim3(n_tiles, k), dim3(64), 0, c->stream>>>(c->frames, c->frame_stride, s0 + a, W.map_dev, W.words_dev + a, c->boxes_dev, keep_far);
                 if (keep_far)
-                    k_whole_far<<<dim3((uint32_t)((W.n_far + 255) / 256), k), dim3(256), 0, c->stream>>>(c->frames, c->frame_stride, s0 + a, W.far_dev, (uint32_t)W.n_far,
+                    k_whole_far<<<dim3((uint32_t)((W.n_far + 255) / 256), k), dim3(256), 0, c->stream>>>(c->frames, c->frame_stride, s0 + a, W.far_dev.get(), (uint32_t)W.n_far,
                                                                                                     W.words_dev + a, c->boxes_dev);
                 HIPCHK(c, hipGetLastError());
             }
@@ -277,7 +272,6 @@ static void whole_release(gr_ctx *c) {
     if (!W) return;
     if (W->map_dev) (void)hipFree(W->map_dev);
     if (W->rank_dev) (void)hipFree(W->rank_dev);
-    if (W->far_dev) (void)hipFree(W->far_dev);
     if (W->words_dev) (void)hipFree(W->words_dev);
     if (W->words_host) (void)hipHostFree(W->words_host);
     delete W;

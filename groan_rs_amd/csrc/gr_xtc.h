@@ -330,7 +330,8 @@ inline uint32_t peek_bits(const unsigned char *p, uint64_t bitpos, int n) {   //
 // n_stop < n: PARTIAL skim (GroupXtcReader, molly_xtc.rs:475-560): stop at the first group that starts at or behind atom n_stop;
 // the checkpoints then cover atoms [0, n_end) and d.nbytes is the length of the stream prefix they need.  have_bytes: the
 // prefix of the stream that is in memory -- walking past it is XTC_E_RANGE (the caller reads more and walks again).
-inline int skim_frame(const unsigned char *stream, const FrameIndex &fi, uint32_t n, FrameDesc &d, std::vector<Checkpoint> &cps, uint32_t n_stop = 0xFFFFFFFFu,
+// (aligned: where the function landed decided the speed of the walk, 0.38 or 0.52 ms per frame: profiles/ctx_buffers_call_cost.md)
+__attribute__((aligned(64))) inline int skim_frame(const unsigned char *stream, const FrameIndex &fi, uint32_t n, FrameDesc &d, std::vector<Checkpoint> &cps, uint32_t n_stop = 0xFFFFFFFFu,
                       uint64_t have_bytes = ~0ull) {
     if (n_stop > n) n_stop = n;
     for (int k = 0; k < 3; ++k) { d.minint[k] = fi.minint[k]; d.sizeint[k] = (uint32_t)fi.maxint[k] - (uint32_t)fi.minint[k] + 1u; }
