@@ -24,6 +24,7 @@ CENTER_NAIVE, CENTER_ESTIMATE, CENTER_PBC = 0, 1, 2
 GM_COUNT, GM_X, GM_Y, GM_Z = 0, 1, 2, 3
 GM_WRAP, GM_FORCE_GLOBAL = 1, 2
 GM_STAT_LDS_LAUNCHES, GM_STAT_GLOBAL_LAUNCHES, GM_STAT_LDS_BUDGET = 1, 2, 3
+SEG_STAT_TEAM4, SEG_STAT_TEAM16, SEG_STAT_WAVE, SEG_STAT_WORKGROUP, SEG_STAT_LAST_LAUNCHES, SEG_STAT_LAST_LAUNCH_SETS = 1, 2, 3, 4, 5, 6
 
 # every symbol include/groan_hip.h declares: name -> (restype, argtypes)
 SIGNATURES = {
@@ -148,6 +149,16 @@ SIGNATURES = {
     "gr_gridmap_clear": (C.c_int, [C.c_void_p]),
     "gr_gridmap_accumulate_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "gr_gridmap_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gr_segments_create": (C.c_void_p, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, c_i32p]),
+    "gr_segments_from_labels": (C.c_void_p, [C.c_void_p, C.c_char_p, C.c_void_p, c_i32p]),
+    "gr_segments_from_molecules": (C.c_void_p, [C.c_void_p, c_i32p]),
+    "gr_segments_destroy": (None, [C.c_void_p]),
+    "gr_segments_count": (C.c_uint64, [C.c_void_p]),
+    "gr_segments_sizes": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gr_segments_atoms": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, c_u64p]),
+    "gr_segments_stat": (C.c_int, [C.c_void_p, C.c_int, c_u64p]),
+    "gr_segments_center_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "gr_segments_center_batch_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_void_p), c_u64p, C.c_void_p]),
     "gr_group_center_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "gr_group_translate_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_void_p, C.c_void_p]),
     "gr_group_wrap_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_void_p]),

@@ -3706,3 +3706,4 @@ int gr_synth_uniform(gr_ctx *c, uint32_t slot, const float *box9, uint64_t seed)
 #include "gr_hbonds.h"   // hydrogen bonds: kernels, plan and C ABI (after the context and its helpers)
 #include "gr_whole.h"    // bond topology, make_molecules_whole / make_group_whole: kernels and C ABI
 #include "gr_gridmap.h"  // GridMap: tile maps accumulated over batches of resident frames: geometry, kernels and C ABI
+#include "gr_segments.h" // Segments: per-residue / per-molecule centres of resident frames: partition, kernel and C ABI

@@ -40,6 +40,7 @@ typedef struct gr_ctx gr_ctx;
 typedef struct gr_rmsd_plan gr_rmsd_plan;
 typedef struct gr_hbond_plan gr_hbond_plan;
 typedef struct gr_gridmap gr_gridmap;
+typedef struct gr_segments gr_segments;
 typedef struct gr_xtc gr_xtc;
 
 /* status codes; 1..7 map onto the reference's error enums (src/errors.rs) */
@@ -529,6 +530,57 @@ int gr_gridmap_accumulate_batch(gr_gridmap *map, uint32_t first_slot, uint32_t n
                                 const float *offset /* [n_frames] or NULL */, int flags,
                                 uint64_t *n_outside /* [n_frames] or NULL */, int *status_out /* [n_frames] or NULL */);
 int gr_gridmap_read(gr_gridmap *map, uint64_t *count, int64_t *sum_q, float *mean);
+
+/* ---------------------------------------------------------------- Segments: per-residue / per-molecule centres over resident frames
+ * The loop `for part in group_split_by_resid(..) { group_get_com(part) }` (src/system/groups.rs:344-435, :514-558) or over
+ * molecule_iter (iterating.rs:238-245), run every frame: here the parts are ONE object -- an ordered list of M non-empty, strictly
+ * ascending atom lists ("segments"; they may overlap, atoms may belong to none) -- and the centres of all of them, for a block of
+ * resident frames, are one call.  The object keeps a pointer to its context: destroy it first.
+ *   gr_segments_create         explicit lists, CSR: offsets[n_segments + 1] into `atoms`.  GR_E_INVALID_ARG for NULL pointers, offsets
+ *                              that decrease or a list that is not strictly ascending; GR_E_EMPTY_GROUP for n_segments == 0 or an empty
+ *                              segment; GR_E_OUT_OF_RANGE (gr_last_error_index = the atom) for an atom >= n_atoms.
+ *   gr_segments_from_labels    group_split_by_resid / group_split_by_resname (groups.rs:391-435, :514-558) with labels[n_atoms] (the
+ *                              residue numbers; for names, one number per distinct name): the atoms of `group` (NULL: all atoms) in
+ *                              index order, an atom joins the segment of its label, a label seen for the first time opens a new
+ *                              segment at the END (the reference's IndexMap order, "the order of residues in the system"); atoms of one
+ *                              label that are not adjacent land in the same segment.  GR_E_GROUP_NOT_FOUND, GR_E_EMPTY_GROUP.
+ *   gr_segments_from_molecules one segment per molecule of the bond topology (gr_add_bond), ordered by lowest atom, atoms ascending; an
+ *                              atom without bonds is a segment of its own (what molecule_iter yields for it).  A snapshot: later bond
+ *                              changes do not change the object.
+ *   gr_segments_count, _sizes (out[M]), _atoms (segment s: *n = its size, at most `cap` atoms written, out may be NULL)
+ *   gr_segments_stat           GR_SEG_STAT_TEAM4 / _TEAM16 / _WAVE / _WORKGROUP: segments of each team class (below);
+ *                              GR_SEG_STAT_LAST_LAUNCHES / _LAST_LAUNCH_SETS: kernel launches / launch sets of the last centre call
+ *   gr_segments_center_batch   out[f][s][0..2] = the centre gr_group_center_batch(kind, weighted) gives for segment s as a group in
+ *                              frame f, for the n_frames slots from first_slot: GR_CENTER_NAIVE, _ESTIMATE or _PBC, the same per-atom
+ *                              arithmetic and closing formulas (the f32 terms added in f64), the same box checks per frame (none for
+ *                              GR_CENTER_NAIVE; strict mode included).  Segments are independent calls in the reference: a segment
+ *                              with an atom without position (or mass, when weighted) is NaN, every other segment of the frame keeps
+ *                              its value; status_out[f] is the status of the FIRST failing segment in segment order, with the index
+ *                              gr_group_center_batch reports for that segment as a group.  A frame that fails its box check is NaN
+ *                              everywhere.  Return value, message and gr_last_error_index: the first failed frame (batch rules below).
+ *                              Any number of frames (the device block holds one 1024-frame piece at a time).
+ *   gr_segments_center_batch_device  the same, left on the device: *out_dev -> [n_frames][M][3], valid until the next call on the same
+ *                              object, read with gr_device_read; at most 1024 frames (GR_E_INVALID_ARG beyond); *n_segments = M
+ *                              (out_dev and n_segments may each be NULL).
+ * Every segment is owned by exactly one TEAM of lanes, chosen by its size when the object is made: <= 4 atoms 4 lanes (16 segments per
+ * wave at a time), <= 16 atoms 16 lanes, <= 4096 atoms one wave, larger one 256-lane workgroup; a call is one launch per class that
+ * has segments.  The team adds its lanes' f64 totals in a fixed tree and runs both stages of a GR_CENTER_PBC centre back to back;
+ * no atomics touch the sums, so a segment's result depends on its atoms, its class and the frame only -- not on its neighbours, the
+ * batch or the run. */
+enum { GR_SEG_STAT_TEAM4 = 1, GR_SEG_STAT_TEAM16 = 2, GR_SEG_STAT_WAVE = 3, GR_SEG_STAT_WORKGROUP = 4, GR_SEG_STAT_LAST_LAUNCHES = 5,
+       GR_SEG_STAT_LAST_LAUNCH_SETS = 6 };
+gr_segments *gr_segments_create(gr_ctx *ctx, const uint64_t *offsets, const uint64_t *atoms, uint64_t n_segments, int *status);
+gr_segments *gr_segments_from_labels(gr_ctx *ctx, const char *group, const uint64_t *labels /* [n_atoms] */, int *status);
+gr_segments *gr_segments_from_molecules(gr_ctx *ctx, int *status);
+void gr_segments_destroy(gr_segments *seg);
+uint64_t gr_segments_count(const gr_segments *seg);
+int gr_segments_sizes(const gr_segments *seg, uint64_t *out /* [M] */);
+int gr_segments_atoms(const gr_segments *seg, uint64_t s, uint64_t *out, uint64_t cap, uint64_t *n);
+int gr_segments_stat(const gr_segments *seg, int key, uint64_t *value);
+int gr_segments_center_batch(gr_segments *seg, uint32_t first_slot, uint32_t n_frames, int kind, int weighted,
+                             float *out /* [n_frames][M][3] */, int *status_out /* [n_frames] or NULL */);
+int gr_segments_center_batch_device(gr_segments *seg, uint32_t first_slot, uint32_t n_frames, int kind, int weighted,
+                                    float **out_dev, uint64_t *n_segments, int *status_out);
 
 /* ---------------------------------------------------------------- per-frame analyses over a batch of slots
  * The calls above for `n_frames` consecutive slots in ONE set of launches and one read-back (a trajectory loop of

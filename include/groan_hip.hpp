@@ -739,4 +739,86 @@ class GridMap {
     std::pair<float, float> span_x_{ 0.f, 0.f }, span_y_{ 0.f, 0.f }, tile_{ 0.f, 0.f };
 };
 
+// ---- Segments: the centres of every residue / molecule / listed part, for a block of resident frames, in one call
+// (the loop over group_split_by_resid / molecule_iter + group_get_com of each part: groups.rs:344-435, iterating.rs:238-245)
+enum class CenterKind : int { Naive = GR_CENTER_NAIVE, Estimate = GR_CENTER_ESTIMATE, Pbc = GR_CENTER_PBC };
+
+class Segments {
+  public:
+    // explicit atom lists, each strictly ascending; they may overlap
+    static Segments from_lists(System &system, const std::vector<std::vector<uint64_t>> &lists) {
+        std::vector<uint64_t> off(lists.size() + 1, 0), atoms;
+        for (size_t s = 0; s < lists.size(); ++s) { off[s + 1] = off[s] + lists[s].size(); atoms.insert(atoms.end(), lists[s].begin(), lists[s].end()); }
+        if (atoms.empty()) atoms.push_back(0);
+        Segments g(system.raw());
+        int st = 0;
+        g.seg_ = gr_segments_create(g.ctx_, off.data(), atoms.data(), lists.size(), &st);
+        if (!g.seg_) g.raise(st);
+        return g;
+    }
+    // group_split_by_resid (labels = residue numbers) / group_split_by_resname (one number per name): labels[n_atoms]; group "" = all atoms
+    static Segments from_labels(System &system, const std::vector<uint64_t> &labels, const std::string &group = "") {
+        if (labels.size() != gr_n_atoms(system.raw())) throw std::invalid_argument("Segments::from_labels | one label per atom");
+        Segments g(system.raw());
+        int st = 0;
+        g.seg_ = gr_segments_from_labels(g.ctx_, group.empty() ? nullptr : group.c_str(), labels.data(), &st);
+        if (!g.seg_) g.raise(st);
+        return g;
+    }
+    // one segment per molecule of the bonds as they are now; an atom without bonds is a segment of its own
+    static Segments from_molecules(System &system) {
+        Segments g(system.raw());
+        int st = 0;
+        g.seg_ = gr_segments_from_molecules(g.ctx_, &st);
+        if (!g.seg_) g.raise(st);
+        return g;
+    }
+    ~Segments() { if (seg_) gr_segments_destroy(seg_); }
+    Segments(const Segments &) = delete;
+    Segments &operator=(const Segments &) = delete;
+    Segments(Segments &&o) noexcept : ctx_(o.ctx_), seg_(o.seg_) { o.seg_ = nullptr; }
+
+    uint64_t size() const { return gr_segments_count(seg_); }
+    std::vector<uint64_t> sizes() const { std::vector<uint64_t> v(size()); gr_segments_sizes(seg_, v.data()); return v; }
+    std::vector<uint64_t> atoms(uint64_t s) const {
+        uint64_t n = 0;
+        int st = gr_segments_atoms(seg_, s, nullptr, 0, &n);
+        if (st != GR_OK) raise(st);
+        std::vector<uint64_t> v(n);
+        gr_segments_atoms(seg_, s, v.data(), n, &n);
+        return v;
+    }
+    uint64_t stat(int key) const { uint64_t v = 0; if (gr_segments_stat(seg_, key, &v) != GR_OK) throw std::invalid_argument("Segments::stat | unknown key"); return v; }
+    // [n_frames][M][3]; NaN for a segment with an atom without position / mass and for every segment of a frame that fails its box
+    // check.  A failed frame throws the first failure unless `status` is given, which then receives every frame's status
+    std::vector<float> centers(uint32_t first_slot, uint32_t n_frames, CenterKind kind, bool weighted, std::vector<int> *status = nullptr) {
+        std::vector<float> out((size_t)n_frames * size() * 3);
+        std::vector<int> st(n_frames);
+        const int r = gr_segments_center_batch(seg_, first_slot, n_frames, (int)kind, weighted ? 1 : 0, out.data(), st.data());
+        if (status) *status = st;
+        else if (r != GR_OK) raise(r);
+        return out;
+    }
+    std::vector<float> get_com(uint32_t first_slot, uint32_t n_frames, std::vector<int> *status = nullptr) { return centers(first_slot, n_frames, CenterKind::Pbc, true, status); }
+    std::vector<float> get_center(uint32_t first_slot, uint32_t n_frames, std::vector<int> *status = nullptr) { return centers(first_slot, n_frames, CenterKind::Pbc, false, status); }
+    gr_segments *raw() const { return seg_; }
+
+  private:
+    explicit Segments(gr_ctx *ctx) : ctx_(ctx) {}
+    [[noreturn]] void raise(int st) const {
+        const uint64_t idx = gr_last_error_index(ctx_);
+        switch (st) {
+        case GR_E_GROUP_NOT_FOUND: throw Error("GroupError", "NotFound", st);
+        case GR_E_EMPTY_GROUP: throw Error("GroupError", "EmptyGroup", st);
+        case GR_E_NO_POSITION: throw Error("GroupError", "InvalidPosition", st, idx);
+        case GR_E_NO_MASS: throw Error("GroupError", "InvalidMass", st, idx);
+        case GR_E_OUT_OF_RANGE: throw Error("AtomError", "OutOfRange", st, idx);
+        case GR_E_NO_BOX: case GR_E_NOT_ORTHOGONAL: case GR_E_ZERO_BOX: throw Error("GroupError", "InvalidSimBox(" + simbox_variant(st) + ")", st);
+        default: throw Error("DeviceError", std::string(gr_status_string(st)) + ": " + gr_last_error(ctx_), st);
+        }
+    }
+    gr_ctx *ctx_ = nullptr;
+    gr_segments *seg_ = nullptr;
+};
+
 }  // namespace groan

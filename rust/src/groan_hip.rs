@@ -41,9 +41,16 @@ pub const GR_GM_Y: c_int = 2;
 pub const GR_GM_Z: c_int = 3;
 pub const GR_GM_WRAP: c_int = 1;
 pub const GR_GM_FORCE_GLOBAL: c_int = 2;
+pub const GR_SEG_STAT_TEAM4: c_int = 1;
+pub const GR_SEG_STAT_TEAM16: c_int = 2;
+pub const GR_SEG_STAT_WAVE: c_int = 3;
+pub const GR_SEG_STAT_WORKGROUP: c_int = 4;
+pub const GR_SEG_STAT_LAST_LAUNCHES: c_int = 5;
+pub const GR_SEG_STAT_LAST_LAUNCH_SETS: c_int = 6;
 
 #[repr(C)] pub struct gr_hbond_plan { _private: [u8; 0] }
 #[repr(C)] pub struct gr_gridmap { _private: [u8; 0] }
+#[repr(C)] pub struct gr_segments { _private: [u8; 0] }
 #[repr(C)] pub struct gr_pool { _private: [u8; 0] }
 #[repr(C)] pub struct gr_comm { _private: [u8; 0] }
 /// `body(ctx, worker, frame, user, result)` of gr_pool_map: non-zero return = the frame's error (the first one wins)
@@ -154,6 +161,18 @@ extern "C" {
     pub fn gr_gridmap_accumulate_batch(map: *mut gr_gridmap, first_slot: u32, n_frames: u32, group: *const c_char, value: c_int, offset: *const c_float,
                                        flags: c_int, n_outside: *mut u64, status_out: *mut c_int) -> c_int;
     pub fn gr_gridmap_read(map: *mut gr_gridmap, count: *mut u64, sum_q: *mut i64, mean: *mut c_float) -> c_int;
+    // Segments: the loop over group_split_by_resid / molecule_iter + group_get_com of each part (groups.rs:344-435, iterating.rs:238-245) as one call
+    pub fn gr_segments_create(ctx: *mut gr_ctx, offsets: *const u64, atoms: *const u64, n_segments: u64, status: *mut c_int) -> *mut gr_segments;
+    pub fn gr_segments_from_labels(ctx: *mut gr_ctx, group: *const c_char, labels: *const u64, status: *mut c_int) -> *mut gr_segments;
+    pub fn gr_segments_from_molecules(ctx: *mut gr_ctx, status: *mut c_int) -> *mut gr_segments;
+    pub fn gr_segments_destroy(seg: *mut gr_segments);
+    pub fn gr_segments_count(seg: *const gr_segments) -> u64;
+    pub fn gr_segments_sizes(seg: *const gr_segments, out: *mut u64) -> c_int;
+    pub fn gr_segments_atoms(seg: *const gr_segments, s: u64, out: *mut u64, cap: u64, n: *mut u64) -> c_int;
+    pub fn gr_segments_stat(seg: *const gr_segments, key: c_int, value: *mut u64) -> c_int;
+    pub fn gr_segments_center_batch(seg: *mut gr_segments, first_slot: u32, n_frames: u32, kind: c_int, weighted: c_int, out: *mut c_float, status_out: *mut c_int) -> c_int;
+    pub fn gr_segments_center_batch_device(seg: *mut gr_segments, first_slot: u32, n_frames: u32, kind: c_int, weighted: c_int,
+                                           out_dev: *mut *mut c_float, n_segments: *mut u64, status_out: *mut c_int) -> c_int;
     pub fn gr_ctx_set_tuning(ctx: *mut gr_ctx, key: c_int, value: i64) -> c_int;   // GR_TUNE_* (include/groan_hip.h)
     pub fn gr_host_alloc(bytes: usize) -> *mut c_void;                              // pinned memory: asynchronous gr_frame_upload
     pub fn gr_host_free(p: *mut c_void);
