@@ -396,9 +396,12 @@ int gr_hbond_batch(gr_hbond_plan *p, uint32_t first_slot, uint32_t n_frames, uin
     const size_t n_rb = (size_t)nf * np + 1;
     const size_t o_fr = 0, o_cc = o_fr + hb_al(sizeof(GrHbFrame) * nf), o_cs = o_cc + hb_al(4 * (nkeys + 1)), o_key = o_cs + hb_al(4 * (nkeys + 1)),
                  o_rank = o_key + hb_al(4 * n_el), o_sort = o_rank + hb_al(4 * n_el), o_cnt = o_sort + hb_al(16 * n_el), o_off = o_cnt + hb_al(4 * (n_t + 1)),
-                 o_rb = o_off + hb_al(8 * (n_t + 1)), o_dbad = o_rb + hb_al(8 * n_rb), o_abad = o_dbad + 8 * (size_t)nf, o_tmp = o_abad + hb_al(4 * (size_t)nf),
+                 o_rb = o_off + hb_al(8 * (n_t + 1)), o_dbad = o_rb + hb_al(8 * n_rb), o_abad = o_dbad + hb_al(8 * (size_t)nf), o_tmp = o_abad + hb_al(4 * (size_t)nf),
                  ws_bytes = o_tmp + hb_al(std::max(tmp_cells, tmp_lanes));
     const size_t rb_bytes = o_tmp - o_rb;                                           // offsets + error words: one read-back
+    // every block starts on a 256-byte line, the scans' temporary storage included: rocprim lays its storage out from the pointer it is
+    // given and needs its 16-byte look-back states aligned
+    if ((o_cc | o_cs | o_key | o_rank | o_sort | o_cnt | o_off | o_rb | o_dbad | o_abad | o_tmp) & 255) return fail(c, GR_E_INVALID_ARG, "hydrogen-bond workspace: a block is off its 256-byte line");
     HIPCHK(c, p->ws.reserve(ws_bytes, grbuf::quarter_aligned256));
     HIPCHK(c, p->hbuf.reserve(hb_al(sizeof(GrHbFrame) * nf) + rb_bytes, grbuf::quarter_aligned256));
     unsigned char *W = p->ws.get();

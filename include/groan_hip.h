@@ -276,7 +276,8 @@ uint32_t gr_rmsd_plan_last_fallbacks(const gr_rmsd_plan *plan);
 /* force the multi-pass exact path (parity testing of both paths) */
 int gr_rmsd_plan_force_exact(gr_rmsd_plan *plan, int on);
 /* Launch geometry and path selection of the batched RMSD calls.  Nothing in the library reads the environment for these:
- * results of a call depend on its arguments and on what the caller set here, never on the caller's environment.
+ * results of a call depend on its arguments and on what the caller set here, never on the caller's environment, nor on earlier calls
+ * on the same context (`tests/test_gpu_history.py`).
  *   GR_TUNE_SUB_BATCH  frames per sums -> fit launch group (1 .. 1024, default 256)
  *   GR_TUNE_CHUNKS     workgroups per frame of the reduction kernels (0 = automatic)
  *   GR_TUNE_FIT_WGS    workgroups per frame of the fit kernel (0 = automatic: one 256-atom tile per wave)

@@ -1,0 +1,770 @@
+"""One deterministic world, a table of call kinds and seeded schedules over them: the material of tests/test_gpu_history.py, which
+checks that a call's result does not depend on what its context did before (test_history_schedule.py checks this module on the CPU).
+
+The world: 12 003 atoms (no multiple of 4 or 256; three resident workgroups, the last one ragged) as 4 001 water-like molecules O H H,
+frames = one base configuration plus a little noise, every atom wrapped into its cell on its own (so the molecules on a cell face are
+broken), 400 donor-acceptor pairs placed 0.28 nm apart with the hydrogen on the line.  Slots 0-7 orthorhombic, 8-15 triclinic (the
+cells of test_gpu_segments.py), slot 16 the noise-free RMSD reference (also slot 0 of a reference System of its own).  Slots 17-40
+are the xtc writer's spool: write_slots takes consecutive slots and the device encoder needs 200 000 atoms in a call, so the frames
+to write are repeated there with copy_frame, as test_gpu_xtc_encoder_device.py repeats its frames.
+
+A kind is a function (world) -> result.  It first puts back, from the pristine host frames, every slot it reads or writes that an
+earlier kind has changed (`World.need`; by set_frame or by upload_async + upload_wait, fixed per kind), makes its calls and returns
+everything they handed back: arrays, statuses, the exception if one was raised (with its atom index), and positions and box of every slot
+it may write.  A kind leaves groups, bonds, masses and tuning as it found them."""
+import functools
+import os
+
+import numpy as np
+
+from groan_rs_amd._lib import E_GROUP_NOT_FOUND, E_HIP, E_NO_BOX, E_NO_POSITION, E_OUT_OF_RANGE, E_UNSUPPORTED_BOX     # the status codes of include/groan_hip.h, for the tests too
+
+F = np.float32
+N, N_MOL, N_FRAMES, REF_SLOT, SPOOL, N_SPOOL = 12003, 4001, 16, 16, 17, 24
+N_SLOTS = SPOOL + N_SPOOL
+BOX = [6.0, 6.4, 5.0]
+TRIC = [6.0, 6.4, 5.0, 0, 0, 1.0, 0, -1.5, 0.8]
+FLAT = [12.8942, 29.4173, 3.27353, 0, 0, -4.28403, 0, -1.85917, -4.05997]      # test_gpu_pin_triclinic.py "flat_a": too skewed for the image table
+GRID = (18, 20, 15)              # lattice sites per cell vector, 0.32 to 0.33 nm apart
+USED = (16, 18, 15)              # ... of which the molecules fill these: a gap along x and y (and the unfilled last planes along z) keeps the periodic centre of
+                                 # every group well conditioned -- a group that covers a cell vector evenly has no centre along it
+N_HB_PAIRS = 400
+HB_DISTANCE, HB_ANGLE = 0.3, 150.0
+NAN_SMALL, NAN_BIG, NAN_TAIL, NAN_A40 = 100, 3000, N - 1, 20
+SMALL, SMALL_OTHER, SMALL_XTC = (5, 367), (7, 400), (400, 700)
+RANGES = {"all": (0, N - 1), "small": SMALL, "big": (1003, 6002), "a40": (10, 49), "b50": (1000, 1049), "a300": (300, 599), "b400": (1500, 1899)}
+DEFAULT_TUNING = dict(resident=1, center_resident=1, fuse=1, two_pass=1, small_calls=4096, pairdist_symmetric=1, masked_selections=1, translate_rows=1,
+                      xtc_device_encode=1)
+N_XTC = 6
+NAIVE, ESTIMATE, PBC = 0, 1, 2
+CENTRES = [(NAIVE, 0), (NAIVE, 1), (ESTIMATE, 0), (ESTIMATE, 1), (PBC, 0), (PBC, 1)]
+
+
+def cell(box):
+    """rows = the box vectors (gromacs order xx yy zz xy xz yx yz zx zy)"""
+    b = np.zeros(9); b[:len(box)] = box
+    return np.array([[b[0], b[3], b[4]], [b[5], b[1], b[6]], [b[7], b[8], b[2]]], np.float64)
+
+
+def box_of(slot):
+    return BOX if slot < 8 or slot == REF_SLOT else TRIC
+
+
+# ------------------------------------------------------------------ the host side
+@functools.lru_cache(maxsize=None)
+def host_world():
+    """-> dict: frames [17] float32 [N, 3], boxes [17], masses, bonds, bonds_alt, groups {name: indices}, resid, xtc_frames [N_XTC]"""
+    rng = np.random.default_rng(20261019)
+    nx, ny, nz = USED
+    k, j, i = np.meshgrid(np.arange(nz), np.arange(ny), np.arange(nx), indexing="ij")
+    site = np.stack([i.ravel(), j.ravel(), k.ravel()], 1)[:N_MOL]                   # i runs fastest
+    frac = site / np.array(GRID, np.float64) + rng.uniform(-0.002, 0.002, (N_MOL, 3))
+    # a water molecule in a random orientation: O-H 0.1 nm, H-O-H 104.5 degrees
+    def unit(v):
+        return v / np.linalg.norm(v, axis=1)[:, None]
+    e1 = unit(rng.normal(size=(N_MOL, 3)))
+    e2 = unit(np.cross(e1, rng.normal(size=(N_MOL, 3))))
+    # donors: an even site of the row with its right-hand neighbour, 400 of them spread over the system
+    cand = np.nonzero((site[:, 0] % 2 == 0) & (site[:, 0] + 1 < nx) & (np.arange(N_MOL) + 1 < N_MOL))[0]
+    donors = cand[np.linspace(0, len(cand) - 1, N_HB_PAIRS).astype(int)]
+    assert len(set(donors.tolist())) == N_HB_PAIRS
+    e1[donors] = [1.0, 0.0, 0.0]
+    e2[donors] = unit(np.cross(e1[donors], rng.normal(size=(N_HB_PAIRS, 3))))
+    a = np.deg2rad(104.5)
+    h1, h2 = 0.1 * e1, 0.1 * (np.cos(a) * e1 + np.sin(a) * e2)
+    masses = np.array([1.008, 12.011, 14.007, 15.999], F)[np.arange(N) % 4]
+
+    def frame(box, noise):
+        H = cell(box)
+        o = frac @ H
+        o[donors + 1] = o[donors] + [0.28, 0.0, 0.0]                               # the acceptor, on the line O-H1
+        pos = np.empty((N, 3))
+        pos[0::3], pos[1::3], pos[2::3] = o, o + h1, o + h2
+        if noise is not None:
+            pos += np.repeat(noise.normal(0.0, 0.004, (N_MOL, 3)), 3, axis=0) + noise.normal(0.0, 0.002, (N, 3))
+        u = pos @ np.linalg.inv(H)
+        return ((u - np.floor(u)) @ H).astype(F)                                   # every atom into the cell on its own
+
+    frames = [frame(box_of(f), np.random.default_rng(1000 + f)) for f in range(N_FRAMES)] + [frame(BOX, None)]
+    boxes = [box_of(f) for f in range(N_FRAMES + 1)]
+    xtc_frames = [frame(BOX, np.random.default_rng(2000 + f)) for f in range(N_XTC)]
+    ox = np.arange(0, N, 3)
+    bonds = np.concatenate([np.stack([ox, ox + 1], 1), np.stack([ox, ox + 2], 1)]).astype(np.uint64)
+    bonds_alt = np.concatenate([np.stack([ox, ox + 1], 1), np.stack([ox[:-1] + 2, ox[1:]], 1)[::5]]).astype(np.uint64)      # O-H1 only, and every fifth molecule tied to the next
+    groups = {name: np.arange(a, b + 1) for name, (a, b) in RANGES.items()}
+    groups["masked"] = np.arange(0, 10000, 2)
+    groups["listbig"] = groups["masked"]
+    groups["list"] = np.arange(0, N, 7)
+    groups["oxy"] = ox
+    groups["hyd"] = np.sort(np.concatenate([ox + 1, ox + 2]))
+    return dict(frames=frames, boxes=boxes, masses=masses, bonds=bonds, bonds_alt=bonds_alt, groups=groups, resid=(np.arange(N) // 7).astype(np.uint64),
+                xtc_frames=xtc_frames, donors=donors)
+
+
+def nan_frame(slot, atom):
+    x = host_world()["frames"][slot].copy()
+    x[atom] = np.nan
+    return x
+
+
+# ------------------------------------------------------------------ the device side
+class World:
+    def __init__(self, G, tmp_dir):
+        self.G, self.tmp, self.host = G, str(tmp_dir), host_world()
+        h = self.host
+        self.s = G.System(N, masses=h["masses"], n_slots=N_SLOTS)
+        self.ref = G.System(N, masses=h["masses"], n_slots=1)
+        self.ref.set_frame(h["frames"][REF_SLOT], BOX, slot=0)
+        self.pin, self._pin_ptr = G.pinned_array((N, 3))
+        self.dirty = set()
+        for slot in range(N_FRAMES + 1):
+            self.load(slot, "set_frame")
+        for s in (self.s, self.ref):
+            for name, r in RANGES.items():
+                s.group_create_from_ranges(name, [r])
+            s.group_create_from_indices("masked", h["groups"]["masked"])
+            s.group_create_from_indices("list", h["groups"]["list"])
+            s.group_create_from_indices("oxy", h["groups"]["oxy"])
+            s.group_create_from_indices("hyd", h["groups"]["hyd"])
+            s.set_tuning(masked_selections=0)
+            s.group_create_from_indices("listbig", h["groups"]["listbig"])
+            s.set_tuning(masked_selections=1)
+        self.s.add_bonds(h["bonds"])
+        self.plans = {g: G.RMSDPlan(self.ref, self.s, g) for g in ("all", "big", "masked", "listbig", "small")}
+        self.seg = {"mol": G.Segments.from_molecules(self.s), "resid": G.Segments.by_resid(self.s, h["resid"])}
+        self.hb = G.HBondAnalysis(self.s, [G.HBondChain("oxy", "oxy", "hyd")], [(0, 0)], HB_DISTANCE, HB_ANGLE, h["bonds"])
+        self.map = G.GridMap(self.s, (0.0, 6.0), (0.0, 6.4), (0.25, 0.25))
+        # the trajectories the readers read: written by the host writers
+        self.xtc_path, self.trr_path = os.path.join(self.tmp, "world.xtc"), os.path.join(self.tmp, "world.trr")
+        if not os.path.isfile(self.xtc_path):
+            box9 = np.array(BOX + [0] * 6, F)
+            with G.XtcWriter(self.xtc_path) as wx, G.TrrWriter(self.trr_path) as wt:
+                for f, x in enumerate(h["xtc_frames"]):
+                    wx.write_frame(x, box9, step=10 * f, time=0.5 * f)
+                    wt.write_frame(x[::-1].copy(), box9, step=10 * f, time=0.5 * f)
+        self.xtc, self.trr = G.XtcFile(self.xtc_path), G.TrrFile(self.trr_path)
+        self.n_written = 0
+        self.s.sync()
+
+    def close(self):
+        self.xtc.close(); self.trr.close()
+        self.s.close(); self.ref.close()
+        self.G.pinned_free(self._pin_ptr)
+
+    # -- slots
+    def load(self, slot, how, frame=None, box="pristine"):
+        x = self.host["frames"][slot] if frame is None else frame
+        b = self.host["boxes"][slot] if isinstance(box, str) else box
+        if how == "set_frame":
+            self.s.set_frame(x, b, slot=slot)
+        else:
+            self.pin[:] = x
+            self.s.upload_async(self.pin, b, slot)
+            self.s.upload_wait(slot)
+        if frame is None and isinstance(box, str):
+            self.dirty.discard(slot)
+        else:
+            self.dirty.add(slot)
+
+    def need(self, slots, how):
+        for slot in slots:
+            if slot in self.dirty:
+                self.load(slot, how)
+
+    def tune(self, **kw):
+        self.s.set_tuning(**kw)
+
+    def untune(self, *keys):
+        self.s.set_tuning(**{k: DEFAULT_TUNING[k] for k in keys})
+
+
+def make_world(G, tmp_dir):
+    return World(G, tmp_dir)
+
+
+# ------------------------------------------------------------------ kinds
+KINDS, META = {}, {}          # META[name] = dict(family, failing, lean)
+
+
+def _exc(e):
+    d = getattr(e, "detail", None)
+    if isinstance(d, Exception):
+        d = (type(d).__name__, getattr(d, "variant", None), repr(getattr(d, "detail", None)))
+    elif d is not None and not isinstance(d, (int, str, tuple)):
+        d = repr(d)
+    return (type(e).__name__, getattr(e, "variant", None), d, getattr(e, "status", None))
+
+
+def kind(name, family, slots=(), writes=(), failing=False, how="set_frame", lean=False):
+    """register body(w, out) under `name`: `slots` are put back before it, `writes` (a subset) are read back after it"""
+    def deco(body):
+        def run(w):
+            import groan_rs_amd as G
+            w.need(slots, how)
+            out = {}
+            try:
+                body(w, out)
+                out["raised"] = None
+            except (G.GroanError, G.XtcError) as e:
+                if getattr(e, "status", None) == E_HIP:          # the device or the runtime failed: no result to compare, and nothing more to run
+                    raise
+                out["raised"] = _exc(e)                                 # (an atom index is the exception's detail)
+            for slot in writes:
+                out["pos%d" % slot] = w.s.get_positions(slot)
+                b = w.s.get_box(slot)
+                out["box%d" % slot] = None if b is None else np.array(b)
+            w.dirty.update(writes)
+            return out
+        KINDS[name] = run
+        META[name] = dict(family=family, failing=failing, lean=lean)
+        return body
+    return deco
+
+
+R16 = tuple(range(16))
+ORTHO8, TRIC8 = tuple(range(8)), tuple(range(8, 16))
+
+# -- centres
+_CALL = {(NAIVE, 0): "group_get_center_naive", (NAIVE, 1): "group_get_com_naive", (ESTIMATE, 0): "group_estimate_center", (ESTIMATE, 1): "group_estimate_com",
+         (PBC, 0): "group_get_center", (PBC, 1): "group_get_com"}
+for _g in ("small", "big", "masked"):
+    for _k, _w in CENTRES:
+        def _one(w, out, g=_g, k=_k, wt=_w):
+            out["c3"] = getattr(w.s, _CALL[(k, wt)])(g, slot=3)
+            out["c11"] = getattr(w.s, _CALL[(k, wt)])(g, slot=11)
+        kind("center_%s_%d%d" % (_g, _k, _w), "centres", slots=(3, 11))(_one)
+
+        def _batch(w, out, g=_g, k=_k, wt=_w):
+            out["c"], out["st"] = w.s.group_center_batch(g, k, wt, 0, 16)
+        kind("center_batch_%s_%d%d" % (_g, _k, _w), "centres", slots=R16, how="upload")(_batch)
+
+
+@kind("group_distance", "centres", slots=(3, 11))
+def _(w, out):
+    D = w.G.Dimension
+    out["d"] = F(w.s.group_distance("small", "b400", D.XYZ, slot=3))                # both small: one dispatch, two words
+    out["dxy"] = F(w.s.group_distance("small", "big", D.XY, slot=11))
+
+
+@kind("atoms_center_small", "centres", slots=(3,), writes=(3,))
+def _(w, out):
+    w.s.atoms_center("small", w.G.Dimension.XYZ, slot=3)
+
+
+@kind("atoms_center_mass_big", "centres", slots=(11,), writes=(11,), how="upload")
+def _(w, out):
+    w.s.atoms_center_mass("big", w.G.Dimension.XY, slot=11)
+
+
+def _center_batch(resident, weighted, slots):
+    def body(w, out):
+        w.tune(center_resident=resident, resident=2 if resident else 0)
+        try:
+            before = (w.s.stat("center_res_launches"), w.s.stat("res_lean_segments"))
+            out["st"] = w.s.atoms_center_batch("big", slots[0], len(slots), w.G.Dimension.XYZ, weighted=weighted)
+            out["launches"] = w.s.stat("center_res_launches") - before[0]
+            out["lean"] = w.s.stat("res_lean_segments") - before[1]
+        finally:
+            w.untune("center_resident", "resident")
+    return body
+
+
+kind("atoms_center_batch_res", "centres", slots=ORTHO8, writes=ORTHO8, lean=True)(_center_batch(1, False, ORTHO8))
+kind("atoms_center_mass_batch_res", "centres", slots=TRIC8, writes=TRIC8, how="upload", lean=True)(_center_batch(1, True, TRIC8))
+kind("atoms_center_batch_two", "centres", slots=ORTHO8, writes=ORTHO8)(_center_batch(0, False, ORTHO8))
+kind("atoms_center_mass_batch_two", "centres", slots=TRIC8, writes=TRIC8)(_center_batch(0, True, TRIC8))
+
+
+def _move_batch(call, slots, rows):
+    def body(w, out):
+        w.tune(translate_rows=rows)
+        try:
+            if call == "translate":
+                out["st"] = w.s.group_translate_batch("big", [1.7, -2.9, 0.45], slots[0], len(slots))
+            else:
+                out["st"] = w.s.group_wrap_batch("big", slots[0], len(slots))
+        finally:
+            w.untune("translate_rows")
+    return body
+
+
+for _call in ("translate", "wrap"):
+    kind("%s_batch_ortho_rows1" % _call, "centres", slots=ORTHO8, writes=ORTHO8)(_move_batch(_call, ORTHO8, 1))
+    kind("%s_batch_ortho_rows0" % _call, "centres", slots=ORTHO8, writes=ORTHO8, how="upload")(_move_batch(_call, ORTHO8, 0))
+    kind("%s_batch_tric" % _call, "centres", slots=TRIC8, writes=TRIC8)(_move_batch(_call, TRIC8, 1))
+
+
+@kind("group_translate_small", "centres", slots=(3,), writes=(3,))
+def _(w, out):
+    w.s.group_translate("small", [4.0, -7.0, 0.3], slot=3)
+
+
+@kind("group_wrap_all", "centres", slots=(3,), writes=(3,))
+def _(w, out):
+    w.s.group_translate("all", [-0.4, 0.3, 9.0], slot=3)
+    w.s.group_wrap("all", slot=3)
+
+
+@kind("fail_translate_nan_small", "centres", writes=(3,), failing=True)
+def _(w, out):
+    w.load(3, "set_frame", frame=nan_frame(3, NAN_SMALL))
+    w.s.group_translate("small", [0.1, 0.2, 0.3], slot=3)
+
+
+@kind("fail_com_nan_big", "centres", writes=(11,), failing=True)
+def _(w, out):
+    w.load(11, "upload", frame=nan_frame(11, NAN_BIG))
+    out["c"] = w.s.group_get_com("big", slot=11)
+
+
+@kind("fail_translate_nan_tail", "centres", writes=(3,), failing=True)
+def _(w, out):
+    w.load(3, "set_frame", frame=nan_frame(3, NAN_TAIL))
+    w.s.group_translate("all", [0.1, 0.2, 0.3], slot=3)
+
+
+@kind("fail_center_nobox", "centres", slots=(3,), writes=(3,), failing=True)
+def _(w, out):
+    w.s.reset_box(slot=3)
+    w.dirty.add(3)
+    out["c"] = w.s.group_get_center("big", slot=3)
+
+
+@kind("fail_center_nogroup", "centres", slots=(3,), failing=True)
+def _(w, out):
+    out["c"] = w.s.group_get_com("nobody", slot=3)
+
+
+@kind("fail_center_batch_mixed", "centres", writes=(0, 1, 2, 3, 4, 5), failing=True)
+def _(w, out):
+    w.need((0, 1, 3, 4, 5), "set_frame")
+    w.load(2, "set_frame", box=None)
+    w.load(4, "set_frame", frame=nan_frame(4, NAN_BIG))
+    out["c"], out["st"] = w.s.group_get_com_batch("big", 0, 6, raise_on_error=False)
+
+
+# -- RMSD
+@kind("calc_rmsd_small", "rmsd", slots=(3,))
+def _(w, out):
+    out["r"], out["R"] = w.s.calc_rmsd(w.ref, "small", slot=3, return_rotation=True)
+    out["r"] = F(out["r"])
+
+
+@kind("calc_rmsd_fit_small", "rmsd", slots=(11,), writes=(11,), how="upload")
+def _(w, out):
+    out["r"] = F(w.s.calc_rmsd_and_fit(w.ref, "small", slot=11))
+
+
+def _plan_rmsd(group):
+    def body(w, out):
+        w.tune(resident=0)
+        try:
+            out["r"], out["st"], out["R"] = w.plans[group].rmsd(0, 16, return_rotation=True)
+        finally:
+            w.untune("resident")
+    return body
+
+
+def _plan_fit(group, fuse):
+    def body(w, out):
+        w.tune(resident=0, fuse=fuse)
+        try:
+            out["r"], out["st"] = w.plans[group].rmsd_fit(0, 16)
+        finally:
+            w.untune("resident", "fuse")
+    return body
+
+
+for _g in ("all", "big", "masked", "listbig"):
+    kind("plan_rmsd_%s" % _g, "rmsd", slots=R16)(_plan_rmsd(_g))
+    kind("plan_fit_%s_fuse1" % _g, "rmsd", slots=R16, writes=R16)(_plan_fit(_g, 1))
+    kind("plan_fit_%s_fuse0" % _g, "rmsd", slots=R16, writes=R16, how="upload")(_plan_fit(_g, 0))
+
+
+def _res_fit(nf):
+    def body(w, out):
+        w.tune(resident=2)
+        try:
+            before = (w.s.stat("res_launches"), w.s.stat("res_lean_segments"))
+            out["r"], out["st"] = w.plans["all"].rmsd_fit(0, nf)
+            out["launches"] = w.s.stat("res_launches") - before[0]
+            out["lean"] = w.s.stat("res_lean_segments") - before[1]
+        finally:
+            w.untune("resident")
+    return body
+
+
+for _nf in (3, 9, 2):
+    kind("res_fit_%d" % _nf, "rmsd", slots=tuple(range(_nf)), writes=tuple(range(_nf)), lean=True)(_res_fit(_nf))
+
+
+@kind("plan_begin_end", "rmsd", slots=ORTHO8, writes=ORTHO8)
+def _(w, out):
+    w.plans["big"].begin(0, 8, True)
+    out["r"], out["st"] = w.plans["big"].end()
+
+
+@kind("fail_fit_mixed_fused", "rmsd", writes=tuple(range(9)), failing=True)
+def _(w, out):
+    w.need((0, 1, 3, 4, 6, 7, 8), "set_frame")
+    w.load(2, "set_frame", box=None)
+    w.load(5, "set_frame", frame=nan_frame(5, 4321))
+    w.tune(resident=0, fuse=1)
+    try:
+        out["r"], out["st"] = w.plans["all"].rmsd_fit(0, 9, raise_on_error=False)
+    finally:
+        w.untune("resident", "fuse")
+
+
+@kind("fail_rmsd_nan_small", "rmsd", writes=(3,), failing=True)
+def _(w, out):
+    w.load(3, "set_frame", frame=nan_frame(3, NAN_SMALL))
+    out["r"] = F(w.s.calc_rmsd(w.ref, "small", slot=3))
+
+
+@kind("fail_rmsd_nogroup", "rmsd", slots=(3,), failing=True)
+def _(w, out):
+    out["r"] = F(w.s.calc_rmsd(w.ref, "nobody", slot=3))
+
+
+# -- pair distances
+@kind("atoms_distance", "pairs", slots=(3, 11))
+def _(w, out):
+    D = w.G.Dimension
+    out["d"] = np.array([w.s.atoms_distance(3, 11777, D.XYZ, slot=3), w.s.atoms_distance(0, N - 1, D.XYZ, slot=11), w.s.atoms_distance(5000, 77, D.YZ, slot=11)], F)
+
+
+def _alldist(g1, g2, slot):
+    def body(w, out):
+        out["d"] = w.s.group_all_distances(g1, g2, slot=slot)
+    return body
+
+
+kind("alldist_40x50", "pairs", slots=(3,))(_alldist("a40", "b50", 3))
+kind("alldist_300x400", "pairs", slots=(11,))(_alldist("a300", "b400", 11))
+kind("alldist_masked_self", "pairs", slots=(11,))(_alldist("masked", "masked", 11))
+kind("alldist_small_self", "pairs", slots=(3,))(_alldist("small", "small", 3))
+
+
+@kind("alldist_batch_device_40x50", "pairs", slots=(6, 7, 8, 9))
+def _(w, out):
+    dev, n1, n2, out["st"] = w.s.group_all_distances_batch_device("a40", "b50", 6, 4)
+    out["d"] = w.s.device_read(dev, 0, (4, n1, n2))
+
+
+def _reduce(op, **kw):
+    def body(w, out):
+        out["v"], out["st"] = w.s.group_all_distances_reduce("a300", "b400", op, first_slot=6, n_frames=4, **kw)
+    return body
+
+
+kind("reduce_max", "pairs", slots=(6, 7, 8, 9))(_reduce("max"))
+kind("reduce_min_rows", "pairs", slots=(6, 7, 8, 9))(_reduce("min", per_row=True))
+kind("reduce_count_rows", "pairs", slots=(6, 7, 8, 9))(_reduce("count_below", per_row=True, param=1.5))
+kind("reduce_hist", "pairs", slots=(6, 7, 8, 9))(_reduce("hist", param=3.0, nbins=97))
+
+
+@kind("iter_all_distances", "pairs", slots=(11,))
+def _(w, out):
+    out["d"] = w.s.group_iter("a40", slot=11).all_distances(w.s.group_iter("list", slot=11))
+
+
+@kind("pairs_within", "pairs", slots=(3,))
+def _(w, out):
+    out["i"], out["j"], out["d"] = w.s.group_pairs_within("small", "big", 0.9, slot=3)
+
+
+@kind("geometries_small_all_small", "pairs", slots=(3,))
+def _(w, out):
+    G = w.G
+    shapes = [G.Sphere([0.3, 0.2, 0.2], 1.4)]
+    try:
+        for k, src in enumerate(("small", "all", "small")):
+            w.s.group_create_from_geometries("geo", src, shapes, slot=3)
+            out["blocks%d" % k] = np.array(w.s.group_container("geo").blocks, np.uint64)
+            w.s.group_remove("geo")
+    finally:
+        if w.s.group_exists("geo"):
+            w.s.group_remove("geo")
+
+
+@kind("fail_alldist_skewed", "pairs", slots=(3,), writes=(3,), failing=True)
+def _(w, out):
+    w.s.set_box(FLAT, slot=3)
+    w.dirty.add(3)
+    out["d"] = w.s.group_all_distances("a40", "b50", slot=3)
+
+
+@kind("fail_alldist_nan", "pairs", writes=(3,), failing=True)
+def _(w, out):
+    w.load(3, "upload", frame=nan_frame(3, NAN_A40))
+    out["d"] = w.s.group_all_distances("a40", "b50", slot=3)
+
+
+@kind("fail_reduce_mixed", "pairs", writes=(6, 7, 8, 9), failing=True)
+def _(w, out):
+    w.need((6, 9), "set_frame")
+    w.load(7, "set_frame", box=None)
+    w.load(8, "set_frame", frame=nan_frame(8, 350))
+    out["v"], out["st"] = w.s.group_all_distances_reduce("a300", "b400", "hist", param=3.0, nbins=97, first_slot=6, n_frames=4, raise_on_error=False)
+
+
+@kind("fail_pairs_nogroup", "pairs", slots=(3,), failing=True)
+def _(w, out):
+    out["d"] = w.s.group_all_distances("a40", "nobody", slot=3)
+
+
+# -- topology
+@kind("whole_mols", "topology", slots=R16, writes=R16)
+def _(w, out):
+    out["st"] = w.s.make_molecules_whole_batch(0, 16)
+
+
+@kind("whole_group_big", "topology", slots=R16, writes=R16, how="upload")
+def _(w, out):
+    out["st"] = w.s.make_group_whole_batch("big", 0, 16)
+
+
+@kind("rebond_whole", "topology", slots=R16, writes=R16)
+def _(w, out):
+    try:
+        w.s.clear_bonds()
+        out["no_bonds"] = int(w.s.has_bonds())
+        w.s.add_bonds(w.host["bonds_alt"])
+        out["st"] = w.s.make_molecules_whole_batch(0, 16)
+    finally:
+        w.s.clear_bonds()
+        w.s.add_bonds(w.host["bonds"])
+
+
+def _segments(which, first, nf):
+    def body(w, out):
+        out["c"], out["st"] = w.seg[which].centers(first, nf, PBC, 1)
+    return body
+
+
+for _which in ("mol", "resid"):
+    kind("seg_%s_2" % _which, "topology", slots=(7, 8))(_segments(_which, 7, 2))
+    kind("seg_%s_9" % _which, "topology", slots=tuple(range(4, 13)))(_segments(_which, 4, 9))
+    kind("seg_%s_1" % _which, "topology", slots=(11,))(_segments(_which, 11, 1))
+
+
+def _hbonds(first, nf):
+    def body(w, out):
+        r = w.hb.batch(first, nf)
+        for name, a in zip(("donor", "hydrogen", "acceptor", "distance", "angle", "offsets", "st"), r):
+            out[name] = a
+    return body
+
+
+kind("hbond_2", "topology", slots=(7, 8))(_hbonds(7, 2))
+kind("hbond_8", "topology", slots=tuple(range(4, 12)))(_hbonds(4, 8))
+kind("hbond_1", "topology", slots=(3,))(_hbonds(3, 1))
+
+
+@kind("gridmap", "topology", slots=ORTHO8)
+def _(w, out):
+    w.map.clear()
+    out["outside"], out["st"] = w.map.accumulate("all", 0, 8, value=w.G.Dimension.Z)
+    out["counts"], out["sums_q"], out["mean"] = w.map.counts, w.map.sums_q, w.map.mean()
+
+
+@kind("fail_seg_nobox", "topology", writes=(4, 5, 6, 7), failing=True)
+def _(w, out):
+    w.need((4, 6, 7), "set_frame")
+    w.load(5, "set_frame", box=None)
+    out["c"], out["st"] = w.seg["mol"].centers(4, 4, PBC, 1, raise_on_error=False)
+
+
+@kind("fail_whole_nan", "topology", writes=(3,), failing=True)
+def _(w, out):
+    w.load(3, "set_frame", frame=nan_frame(3, NAN_BIG))
+    w.s.make_molecules_whole(slot=3)
+
+
+@kind("fail_hbond_mixed", "topology", writes=(4, 5, 6), failing=True)
+def _(w, out):
+    w.need((4,), "set_frame")
+    w.load(5, "set_frame", box=None)
+    w.load(6, "set_frame", frame=nan_frame(6, NAN_BIG))
+    r = w.hb.batch(4, 3, raise_on_error=False)
+    for name, a in zip(("donor", "hydrogen", "acceptor", "distance", "angle", "offsets", "st"), r):
+        out[name] = a
+
+
+# -- trajectory I/O
+def _xtc_write(count, repeat):
+    def body(w, out):
+        for k in range(count * repeat):
+            w.s.copy_frame(SPOOL + k, k % count)
+        w.tune(xtc_device_encode=1)
+        took = w.s.stat("xtc_device_frames")
+        w.n_written += 1
+        path = os.path.join(w.tmp, "out_%d_%d.xtc" % (id(w), w.n_written))
+        nf = count * repeat
+        with w.G.XtcWriter(path) as wr:
+            wr.write_slots(w.s, SPOOL, nf, steps=np.arange(nf, dtype=np.int64) * 10, times=np.arange(nf, dtype=F) * 0.5, host_threads=2)
+        out["device_frames"] = w.s.stat("xtc_device_frames") - took
+        out["bytes"] = open(path, "rb").read()
+        os.remove(path)
+    return body
+
+
+kind("xtc_write_4", "io", slots=(0, 1, 2, 3))(_xtc_write(4, 5))
+kind("xtc_write_12", "io", slots=tuple(range(12)), how="upload")(_xtc_write(12, 2))
+
+
+def _xtc_read(group, first, nf):
+    def body(w, out):
+        out["steps"], out["times"] = w.xtc.read_frames_device(w.s, first, nf, first_slot=0, group=group)
+    return body
+
+
+kind("xtc_read_small", "io", slots=(0, 1, 2, 3), writes=(0, 1, 2, 3))(_xtc_read("small", 0, 4))
+kind("xtc_read_full", "io", slots=(0, 1, 2, 3, 4), writes=(0, 1, 2, 3, 4), how="upload")(_xtc_read(None, 1, 5))
+kind("xtc_read_masked", "io", slots=(0, 1, 2), writes=(0, 1, 2))(_xtc_read("masked", 3, 3))
+kind("xtc_read_full_again", "io", slots=(0, 1), writes=(0, 1))(_xtc_read(None, 4, 2))
+
+
+@kind("xtc_read_small_redefined", "io", slots=(0, 1, 2, 3), writes=(0, 1, 2, 3))
+def _(w, out):
+    try:
+        w.s.group_remove("small")
+        w.s.group_create_from_ranges("small", [SMALL_XTC])
+        out["steps"], out["times"] = w.xtc.read_frames_device(w.s, 0, 4, first_slot=0, group="small")
+    finally:
+        if w.s.group_exists("small"):
+            w.s.group_remove("small")
+        w.s.group_create_from_ranges("small", [SMALL])
+
+
+@kind("trr_read", "io", slots=(0, 1, 2, 3, 4, 5), writes=(0, 1, 2, 3, 4, 5))
+def _(w, out):
+    out["steps"], out["times"] = w.trr.read_frames_device(w.s, 0, 6, first_slot=0)
+
+
+@kind("fail_xtc_range", "io", slots=(0, 1), writes=(0, 1), failing=True)
+def _(w, out):
+    out["steps"], out["times"] = w.xtc.read_frames_device(w.s, N_XTC - 1, 2, first_slot=0)
+
+
+@kind("fail_xtc_nogroup", "io", slots=(0,), writes=(0,), failing=True)
+def _(w, out):
+    out["steps"], out["times"] = w.xtc.read_frames_device(w.s, 0, 1, first_slot=0, group="nobody")
+
+
+# -- redefinitions
+@kind("fail_redefined_small_plan", "redef", slots=(3,), failing=True)
+def _(w, out):
+    try:
+        w.s.group_remove("small")
+        w.s.group_create_from_ranges("small", [SMALL_OTHER])
+        out["c"] = w.s.group_get_com("small", slot=3)
+        out["r"], out["st"] = w.plans["small"].rmsd(3, 1)
+    finally:
+        if w.s.group_exists("small"):
+            w.s.group_remove("small")
+        w.s.group_create_from_ranges("small", [SMALL])
+
+
+@kind("fail_redef_nogroup", "redef", slots=(3,), failing=True)
+def _(w, out):
+    w.s.group_remove("nobody")
+
+
+@kind("restored_small_plan", "redef", slots=(3, 11))
+def _(w, out):
+    w.s.group_remove("small")
+    w.s.group_create_from_ranges("small", [SMALL_OTHER])
+    w.s.group_remove("small")
+    w.s.group_create_from_ranges("small", [SMALL])
+    out["r"], out["st"] = w.plans["small"].rmsd(3, 1)
+    out["r11"], out["st11"] = w.plans["small"].rmsd(11, 1)
+    out["c"] = w.s.group_get_com("small", slot=3)
+
+
+@kind("masses_changed", "redef", slots=(3,))
+def _(w, out):
+    other = (w.host["masses"][::-1] * F(1.5)).astype(F)
+    try:
+        w.s.set_masses(other)
+        out["c_other"] = w.s.group_get_com("big", slot=3)
+        out["s_other"] = w.s.group_get_com("small", slot=3)
+    finally:
+        w.s.set_masses(w.host["masses"])
+    out["c"] = w.s.group_get_com("big", slot=3)
+    out["s"] = w.s.group_get_com("small", slot=3)
+
+
+@kind("tune_small_calls0", "redef", slots=(3,))
+def _(w, out):
+    w.tune(small_calls=0)
+    try:
+        before = w.s.stat("small_calls")
+        out["c"] = w.s.group_get_com("small", slot=3)
+        out["d"] = F(w.s.group_distance("small", "a40", slot=3))
+        out["small_calls"] = w.s.stat("small_calls") - before
+    finally:
+        w.untune("small_calls")
+    out["c_again"] = w.s.group_get_com("small", slot=3)
+
+
+@kind("tune_pairsym0", "redef", slots=(3,))
+def _(w, out):
+    w.tune(pairdist_symmetric=0)
+    try:
+        out["d"] = w.s.group_all_distances("small", "small", slot=3)
+    finally:
+        w.untune("pairdist_symmetric")
+
+
+@kind("tune_masked0", "redef", slots=R16)
+def _(w, out):
+    w.tune(masked_selections=0)
+    try:
+        out["c"], out["st"] = w.s.group_get_com_batch("masked", 0, 16)
+        out["r"], out["rst"] = w.plans["masked"].rmsd(0, 4)
+    finally:
+        w.untune("masked_selections")
+
+
+# ------------------------------------------------------------------ schedules
+ADJACENCIES = {
+    1: ["fail_translate_nan_small", "atoms_center_small", "group_wrap_all", "fail_translate_nan_small"],
+    2: ["fail_fit_mixed_fused", "plan_fit_all_fuse1", "res_fit_9", "atoms_center_batch_res"],
+    3: ["group_distance", "center_small_21", "calc_rmsd_small", "group_distance"],
+    4: ["atoms_distance", "reduce_hist", "alldist_300x400", "alldist_batch_device_40x50", "reduce_count_rows", "alldist_40x50"],
+    5: ["xtc_read_small", "xtc_read_small_redefined", "trr_read", "xtc_read_full"],
+    6: ["fail_seg_nobox", "seg_mol_9", "seg_mol_1"],
+    7: ["hbond_2", "hbond_8", "hbond_1"],
+    8: ["whole_mols", "rebond_whole", "whole_mols"],
+    9: ["res_fit_3", "plan_rmsd_masked", "res_fit_9", "plan_rmsd_masked", "res_fit_2"],
+}
+
+
+def mandatory():
+    return [k for a in sorted(ADJACENCIES) for k in ADJACENCIES[a]]
+
+
+def schedule(seed):
+    """the mandatory adjacencies in order, then a seeded shuffle of (failing kind, kind) pairs: every non-failing kind once directly
+    behind a failing kind of its own family and once behind one of another family, every failing kind at least twice"""
+    rng = np.random.default_rng(seed)
+    fails = {}
+    for name in sorted(KINDS):
+        if META[name]["failing"]:
+            fails.setdefault(META[name]["family"], []).append(name)
+    all_fails = [f for fam in sorted(fails) for f in fails[fam]]
+    turn = {"own": {fam: 0 for fam in fails}, "other": 0}
+    pairs = []
+    for name in sorted(KINDS):
+        if META[name]["failing"]:
+            continue
+        fam = META[name]["family"]
+        own = fails[fam][turn["own"][fam] % len(fails[fam])]; turn["own"][fam] += 1
+        while META[all_fails[turn["other"] % len(all_fails)]]["family"] == fam:
+            turn["other"] += 1
+        other = all_fails[turn["other"] % len(all_fails)]; turn["other"] += 1
+        pairs += [(own, name), (other, name)]
+    order = rng.permutation(len(pairs))
+    return mandatory() + [k for p in order for k in pairs[p]]
