@@ -41,6 +41,7 @@ typedef struct gr_rmsd_plan gr_rmsd_plan;
 typedef struct gr_hbond_plan gr_hbond_plan;
 typedef struct gr_gridmap gr_gridmap;
 typedef struct gr_segments gr_segments;
+typedef struct gr_region gr_region;
 typedef struct gr_xtc gr_xtc;
 
 /* status codes; 1..7 map onto the reference's error enums (src/errors.rs) */
@@ -665,6 +666,59 @@ int gr_shape_triangular_prism(gr_shape *s, const float base1[3], const float bas
 int gr_shape_inside(const gr_shape *s, const float point[3], const float box9[9], int naive, int *inside);
 int gr_group_create_from_geometries(gr_ctx *ctx, uint32_t slot, const char *name, const char *source_group,
                                     const gr_shape *shapes, size_t n_shapes, int naive);
+
+/* ---------------------------------------------------------------- Region: geometry selections over a block of resident frames
+ * The loop `for atom in group_iter(..).filter_geometry(shape)` (src/lib.rs:170-188, iterators.rs:994-1004, :1094-1105) or
+ * group_create_from_geometries (groups.rs:94-188), run every frame: here the shapes are ONE object and the selection of a block of resident
+ * slots is one call.  For every frame: the atoms of a group that have a position and lie inside EVERY shape, in the source group's
+ * iteration order -- the list gr_group_create_from_geometries would make of that frame.  The object keeps a pointer to its context:
+ * destroy it first.
+ *   gr_region_create           up to GR_MAX_SHAPES shapes and the naive flag, validated as by gr_group_create_from_geometries:
+ *                              GR_E_INVALID_ARG for more shapes than that, an invalid kind or orientation, or a prism with `naive`.
+ *                              n_shapes == 0 is allowed: every atom with a position is inside.
+ *   gr_region_select_batch     selects in the n_frames slots from first_slot among the atoms of `group` (NULL: all atoms).
+ *                              anchor (may be NULL: the shapes as stored): the shapes of frame f are the stored ones moved by anchor[f] --
+ *                              position, and for the prism base2 and base3, become stored + anchor[f], one f32 add per component (no fma:
+ *                              the same bits on the host and on the device).  The stored position thus acts as an offset from a
+ *                              per-frame point, e.g. (0, 0, -h/2) from a centre of gr_group_center_batch.  A frame whose anchor has a
+ *                              component that is not finite fails with GR_E_INVALID_ARG (naive or not).
+ *                              Per-frame checks, none of them when naive: GR_E_NO_BOX, the slot's box status (GR_E_ZERO_BOX ...),
+ *                              GR_E_NOT_ORTHOGONAL in strict mode, and GR_E_UNSUPPORTED_BOX where a shape reaches more lattice images
+ *                              of a non-orthogonal cell than the selection enumerates.  An atom without a position is inside nothing;
+ *                              that is not an error.  A failed frame has n_inside[f] = 0 and an empty list, its neighbours are what they
+ *                              are without it; status_out[f] is its status, and the return value, message and gr_last_error_index are
+ *                              the first failed frame's (batch rules below).  GR_E_GROUP_NOT_FOUND fails the whole call; an empty
+ *                              group is no error and gives empty lists (the reference's iterator).  Any number of frames (walked in
+ *                              1024-frame segments); the frames are not modified.  A failed call -- a HIP error, a refused argument --
+ *                              leaves the object with an empty result (0 frames).
+ *                              The result stays on the device, in the object, until the next gr_region_select_batch on it or its
+ *                              destruction: u32 atom indices, frame after frame, and u64 offsets[n_frames + 1] -- offsets[f] ..
+ *                              offsets[f + 1] delimit frame f.  The list is grown to what the call actually selects (the counts of
+ *                              a piece are read back before its lists are written), never sized n_frames x n_atoms.
+ *   gr_region_read             the result on the host, widened to u64: offsets (may be NULL), atoms (NULL: only *n_total is reported;
+ *                              cap < total: GR_E_INVALID_ARG), *n_total (may be NULL)
+ *   gr_region_read_device      the device pointers (read with gr_device_read), the number of frames and of entries; each may be NULL
+ *   gr_region_group            installs frame `frame`'s list as the group `name`: name validation, replacement and GR_E_GROUP_EXISTS as
+ *                              gr_group_create_from_geometries; GR_E_INVALID_ARG for a frame beyond the last call's, or one that failed
+ *   gr_region_set_piece_frames a segment is worked in pieces of frames so that the mask workspace (n/8 bytes per frame) stays within 8 MiB
+ *                              (one frame where that alone is larger); n forces pieces of n frames, 0 restores the default.  The result
+ *                              does not depend on the piece size: the call exists so that piece boundaries can be tested at small sizes.
+ *   gr_region_stat             GR_RG_STAT_LAST_LAUNCHES / _LAST_PIECES: kernel launches / pieces of the last selection; _LAST_TOTAL: its
+ *                              entries; GR_RG_STAT_CHUNK: ordinals of the source group that one workgroup owns (1024)
+ * Per piece three launches: ballot words and per-chunk counts (one workgroup owns one chunk of one frame), an exclusive scan of the
+ * counts per frame, and the lists, where every position is computed from the scans and popcounts.  No atomic decides a position or a
+ * count, so the lists are in ordinal order and the same bits whatever the batch, the piece size, the neighbours or the run. */
+enum { GR_RG_STAT_LAST_LAUNCHES = 1, GR_RG_STAT_LAST_PIECES = 2, GR_RG_STAT_LAST_TOTAL = 3, GR_RG_STAT_CHUNK = 4 };
+gr_region *gr_region_create(gr_ctx *ctx, const gr_shape *shapes, size_t n_shapes, int naive, int *status);
+void gr_region_destroy(gr_region *r);
+int gr_region_select_batch(gr_region *r, uint32_t first_slot, uint32_t n_frames, const char *group /* NULL: all atoms */,
+                           const float *anchor /* [n_frames][3] or NULL */,
+                           uint64_t *n_inside /* [n_frames] or NULL */, int *status_out /* [n_frames] or NULL */);
+int gr_region_read(gr_region *r, uint64_t *offsets /* [n_frames + 1] or NULL */, uint64_t *atoms, uint64_t cap, uint64_t *n_total);
+int gr_region_read_device(gr_region *r, const uint32_t **atoms_dev, const uint64_t **offsets_dev, uint64_t *n_frames, uint64_t *n_total);
+int gr_region_group(gr_region *r, uint32_t frame, const char *name);
+int gr_region_set_piece_frames(gr_region *r, uint32_t n);
+int gr_region_stat(const gr_region *r, int key, uint64_t *value);
 
 /* ---------------------------------------------------------------- xtc reader (host side)
  * The stage in front of the path: XtcReader (src/io/xtc_io/mod.rs, molly_xtc.rs:96-308, xdrfile_xtc.rs:42-104).

@@ -821,4 +821,71 @@ class Segments {
     gr_segments *seg_ = nullptr;
 };
 
+// ---- Region: which atoms of a group lie inside a set of shapes, for every frame of a block of resident frames, in one call
+// (the loop over group_iter(..).filter_geometry(..) / group_create_from_geometries of each frame: src/lib.rs:170-188, groups.rs:94-188)
+class Region {
+  public:
+    Region(System &system, const std::vector<Shape> &shapes, bool naive = false) : ctx_(system.raw()) {
+        std::vector<gr_shape> raw;
+        for (const Shape &s : shapes) raw.push_back(s.c);
+        int st = 0;
+        rg_ = gr_region_create(ctx_, raw.data(), raw.size(), naive ? 1 : 0, &st);
+        if (!rg_) raise(st);
+    }
+    ~Region() { if (rg_) gr_region_destroy(rg_); }
+    Region(const Region &) = delete;
+    Region &operator=(const Region &) = delete;
+    Region(Region &&o) noexcept : ctx_(o.ctx_), rg_(o.rg_) { o.rg_ = nullptr; }
+
+    // the atoms of `group` ("" = all atoms) inside the shapes in n_frames slots from first_slot -> the frames' counts (0 for a failed frame).
+    // anchors: empty, or [n_frames][3] -- the shapes of frame f are the stored ones moved by anchors[f].  A failed frame throws the
+    // first failure unless `status` is given, which then receives every frame's status
+    std::vector<uint64_t> select(const std::string &group, uint32_t first_slot, uint32_t n_frames, const std::vector<float> &anchors = {},
+                                 std::vector<int> *status = nullptr) {
+        if (!anchors.empty() && anchors.size() != (size_t)n_frames * 3) throw std::invalid_argument("Region::select | anchors must hold n_frames x 3 floats");
+        std::vector<uint64_t> counts(n_frames);
+        std::vector<int> st(n_frames);
+        const int r = gr_region_select_batch(rg_, first_slot, n_frames, group.empty() ? nullptr : group.c_str(), anchors.empty() ? nullptr : anchors.data(),
+                                             counts.data(), st.data());
+        if (status) *status = st;
+        else if (r != GR_OK) raise(r);
+        return counts;
+    }
+    // the last selection: offsets[n_frames + 1] and the atom indices, frame after frame
+    std::pair<std::vector<uint64_t>, std::vector<uint64_t>> lists() {
+        uint64_t nf = 0, total = 0;
+        gr_region_read_device(rg_, nullptr, nullptr, &nf, &total);
+        std::vector<uint64_t> off(nf + 1, 0), atoms(total);
+        const int st = gr_region_read(rg_, off.data(), total ? atoms.data() : nullptr, total, nullptr);
+        if (st != GR_OK) raise(st);
+        return { off, atoms };
+    }
+    std::vector<uint64_t> frame(uint32_t f) {
+        auto r = lists();
+        if ((size_t)f + 1 >= r.first.size()) throw std::out_of_range("Region::frame | not a frame of the last selection");
+        return std::vector<uint64_t>(r.second.begin() + (std::ptrdiff_t)r.first[f], r.second.begin() + (std::ptrdiff_t)r.first[f + 1]);
+    }
+    // frame f's list becomes the group `name`; true: a group of that name was replaced (AlreadyExistsWarning)
+    bool to_group(uint32_t f, const std::string &name) {
+        const int st = gr_region_group(rg_, f, name.c_str());
+        if (st == GR_E_INVALID_NAME) throw Error("GroupError", "InvalidName", st);
+        if (st != GR_OK && st != GR_E_GROUP_EXISTS) raise(st);
+        return st == GR_E_GROUP_EXISTS;
+    }
+    void set_piece_frames(uint32_t n) { gr_region_set_piece_frames(rg_, n); }
+    uint64_t stat(int key) const { uint64_t v = 0; if (gr_region_stat(rg_, key, &v) != GR_OK) throw std::invalid_argument("Region::stat | unknown key"); return v; }
+    gr_region *raw() const { return rg_; }
+
+  private:
+    [[noreturn]] void raise(int st) const {
+        switch (st) {
+        case GR_E_GROUP_NOT_FOUND: throw Error("GroupError", "NotFound", st);
+        case GR_E_NO_BOX: case GR_E_NOT_ORTHOGONAL: case GR_E_ZERO_BOX: throw Error("GroupError", "InvalidSimBox(" + simbox_variant(st) + ")", st);
+        default: throw Error("DeviceError", std::string(gr_status_string(st)) + ": " + gr_last_error(ctx_), st);
+        }
+    }
+    gr_ctx *ctx_ = nullptr;
+    gr_region *rg_ = nullptr;
+};
+
 }  // namespace groan

@@ -47,10 +47,15 @@ pub const GR_SEG_STAT_WAVE: c_int = 3;
 pub const GR_SEG_STAT_WORKGROUP: c_int = 4;
 pub const GR_SEG_STAT_LAST_LAUNCHES: c_int = 5;
 pub const GR_SEG_STAT_LAST_LAUNCH_SETS: c_int = 6;
+pub const GR_RG_STAT_LAST_LAUNCHES: c_int = 1;
+pub const GR_RG_STAT_LAST_PIECES: c_int = 2;
+pub const GR_RG_STAT_LAST_TOTAL: c_int = 3;
+pub const GR_RG_STAT_CHUNK: c_int = 4;
 
 #[repr(C)] pub struct gr_hbond_plan { _private: [u8; 0] }
 #[repr(C)] pub struct gr_gridmap { _private: [u8; 0] }
 #[repr(C)] pub struct gr_segments { _private: [u8; 0] }
+#[repr(C)] pub struct gr_region { _private: [u8; 0] }
 #[repr(C)] pub struct gr_pool { _private: [u8; 0] }
 #[repr(C)] pub struct gr_comm { _private: [u8; 0] }
 /// `body(ctx, worker, frame, user, result)` of gr_pool_map: non-zero return = the frame's error (the first one wins)
@@ -173,6 +178,16 @@ extern "C" {
     pub fn gr_segments_center_batch(seg: *mut gr_segments, first_slot: u32, n_frames: u32, kind: c_int, weighted: c_int, out: *mut c_float, status_out: *mut c_int) -> c_int;
     pub fn gr_segments_center_batch_device(seg: *mut gr_segments, first_slot: u32, n_frames: u32, kind: c_int, weighted: c_int,
                                            out_dev: *mut *mut c_float, n_segments: *mut u64, status_out: *mut c_int) -> c_int;
+    // Region: group_iter(..).filter_geometry(..) / group_create_from_geometries for every frame of a block of resident slots
+    pub fn gr_region_create(ctx: *mut gr_ctx, shapes: *const gr_shape, n_shapes: usize, naive: c_int, status: *mut c_int) -> *mut gr_region;
+    pub fn gr_region_destroy(r: *mut gr_region);
+    pub fn gr_region_select_batch(r: *mut gr_region, first_slot: u32, n_frames: u32, group: *const c_char, anchor: *const c_float,
+                                  n_inside: *mut u64, status_out: *mut c_int) -> c_int;
+    pub fn gr_region_read(r: *mut gr_region, offsets: *mut u64, atoms: *mut u64, cap: u64, n_total: *mut u64) -> c_int;
+    pub fn gr_region_read_device(r: *mut gr_region, atoms_dev: *mut *const u32, offsets_dev: *mut *const u64, n_frames: *mut u64, n_total: *mut u64) -> c_int;
+    pub fn gr_region_group(r: *mut gr_region, frame: u32, name: *const c_char) -> c_int;
+    pub fn gr_region_set_piece_frames(r: *mut gr_region, n: u32) -> c_int;
+    pub fn gr_region_stat(r: *const gr_region, key: c_int, value: *mut u64) -> c_int;
     pub fn gr_ctx_set_tuning(ctx: *mut gr_ctx, key: c_int, value: i64) -> c_int;   // GR_TUNE_* (include/groan_hip.h)
     pub fn gr_host_alloc(bytes: usize) -> *mut c_void;                              // pinned memory: asynchronous gr_frame_upload
     pub fn gr_host_free(p: *mut c_void);
