@@ -26,6 +26,8 @@ GM_WRAP, GM_FORCE_GLOBAL = 1, 2
 GM_STAT_LDS_LAUNCHES, GM_STAT_GLOBAL_LAUNCHES, GM_STAT_LDS_BUDGET = 1, 2, 3
 SEG_STAT_TEAM4, SEG_STAT_TEAM16, SEG_STAT_WAVE, SEG_STAT_WORKGROUP, SEG_STAT_LAST_LAUNCHES, SEG_STAT_LAST_LAUNCH_SETS = 1, 2, 3, 4, 5, 6
 RG_STAT_LAST_LAUNCHES, RG_STAT_LAST_PIECES, RG_STAT_LAST_TOTAL, RG_STAT_CHUNK = 1, 2, 3, 4
+CT_STAT_LAST_LAUNCHES, CT_STAT_LAST_PIECES, CT_STAT_LAST_TOTAL, CT_STAT_TILE = 1, 2, 3, 4
+CT_MAX_BINS = 4096
 MAX_SHAPES = 8
 
 # every symbol include/groan_hip.h declares: name -> (restype, argtypes)
@@ -169,6 +171,16 @@ SIGNATURES = {
     "gr_region_group": (C.c_int, [C.c_void_p, C.c_uint32, C.c_char_p]),
     "gr_region_set_piece_frames": (C.c_int, [C.c_void_p, C.c_uint32]),
     "gr_region_stat": (C.c_int, [C.c_void_p, C.c_int, c_u64p]),
+    "gr_contacts_create": (C.c_void_p, [C.c_void_p, C.c_char_p, C.c_char_p, C.c_float, c_i32p]),
+    "gr_contacts_destroy": (None, [C.c_void_p]),
+    "gr_contacts_pairs_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, c_u64p, C.c_void_p]),
+    "gr_contacts_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, c_u64p]),
+    "gr_contacts_read_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), c_u64p, c_u64p]),
+    "gr_contacts_count_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gr_contacts_hist_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "gr_contacts_sizes": (C.c_int, [C.c_void_p, c_u64p, c_u64p]),
+    "gr_contacts_set_piece_frames": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "gr_contacts_stat": (C.c_int, [C.c_void_p, C.c_int, c_u64p]),
     "gr_group_center_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "gr_group_translate_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_void_p, C.c_void_p]),
     "gr_group_wrap_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_void_p]),

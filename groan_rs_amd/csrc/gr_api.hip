@@ -3708,3 +3708,4 @@ int gr_synth_uniform(gr_ctx *c, uint32_t slot, const float *box9, uint64_t seed)
 #include "gr_gridmap.h"  // GridMap: tile maps accumulated over batches of resident frames: geometry, kernels and C ABI
 #include "gr_segments.h" // Segments: per-residue / per-molecule centres of resident frames: partition, kernel and C ABI
 #include "gr_region.h"   // Region: geometry selections over a block of resident frames: kernels, object and C ABI
+#include "gr_contacts.h" // Contacts: cut-off pair search over a block of resident frames: kernels, object and C ABI

@@ -42,6 +42,7 @@ typedef struct gr_hbond_plan gr_hbond_plan;
 typedef struct gr_gridmap gr_gridmap;
 typedef struct gr_segments gr_segments;
 typedef struct gr_region gr_region;
+typedef struct gr_contacts gr_contacts;
 typedef struct gr_xtc gr_xtc;
 
 /* status codes; 1..7 map onto the reference's error enums (src/errors.rs) */
@@ -719,6 +720,63 @@ int gr_region_read_device(gr_region *r, const uint32_t **atoms_dev, const uint64
 int gr_region_group(gr_region *r, uint32_t frame, const char *name);
 int gr_region_set_piece_frames(gr_region *r, uint32_t n);
 int gr_region_stat(const gr_region *r, int key, uint64_t *value);
+
+/* ---------------------------------------------------------------- Contacts: cut-off pair search over a block of resident frames
+ * The loop CellGrid::new + neighbors_iter + distance filter (src/structures/cellgrid.rs:301-409, :434-476, src/system/hbonds.rs:248-265),
+ * run every frame: here the two groups and the cut-off are ONE object and a block of resident slots is one call.  The result of a frame
+ * is exactly what gr_group_pairs_within(ctx, slot, group1, group2, cutoff, ...) gives for that slot: all pairs (i in group1, j in group2,
+ * i != j) with distance(x_j, x_i) <= cutoff, by i then j, d that distance (the same expression on the same bits).  The object keeps a
+ * pointer to its context: destroy it first.
+ *   gr_contacts_create         snapshots the atoms of both groups in group order (later changes to the groups do not change the object).
+ *                              GR_E_GROUP_NOT_FOUND (group1 is looked up first); GR_E_INVALID_ARG unless cutoff > 0 (cellgrid.rs:323-325).
+ *                              Empty groups are allowed.
+ *   per-frame statuses         as gr_group_pairs_within, in its order: GR_E_NO_BOX, the slot's box status, GR_E_NOT_ORTHOGONAL in strict
+ *                              mode; nothing further when either group is empty (no position is looked at); else GR_E_NO_POSITION with
+ *                              gr_last_error_index = the first atom of GROUP 2 (group order) without position, else the first of group 1.
+ *                              A failed frame has 0 pairs, an empty list, a zero per_atom row and a zero histogram row; its neighbours
+ *                              are what they are without it.  status_out[f] is the frame's status, and the return value, message and
+ *                              index are the first failed frame's (batch rules below).  Any number of frames (walked in 1024-frame
+ *                              segments); the frames are not modified.  A hard error -- HIP, a refused argument -- leaves the object
+ *                              with an empty result of 0 frames.
+ *   gr_contacts_pairs_batch    the pair lists of n_frames slots from first_slot, left on the device in the object until the next
+ *                              gr_contacts_pairs_batch on it or its destruction: u32 i, u32 j, f32 d, frame after frame, and u64
+ *                              offsets[n_frames + 1].  The lists are grown to what the call actually finds (the counts of a piece are
+ *                              read back before its lists are written), never sized n1 x n2.  When the call's total exceeds max_pairs no
+ *                              list is kept (count only): n_pairs, *n_total and the offsets are still right, gr_contacts_read with list
+ *                              pointers returns GR_E_INVALID_ARG, and GR_CT_STAT_LAST_TOTAL reports the total.
+ *   gr_contacts_read           the last pairs call on the host: offsets (may be NULL); i, j, d (all NULL: only totals are reported;
+ *                              cap < total: GR_E_INVALID_ARG); *n_total (may be NULL)
+ *   gr_contacts_read_device    the device pointers (read with gr_device_read; NULL lists after a count-only call), frames and pairs
+ *   gr_contacts_count_batch    the same walk without the lists: per_atom[f][k] = pairs of the k-th atom of group1 in frame f,
+ *                              n_pairs[f] their sum -- exactly what the lists would give.  Does not touch the stored lists.
+ *   gr_contacts_hist_batch     hist[f][b] over [0, cutoff) by the rule of GR_PD_HIST applied to the pairs of the list: s = (float)nbins /
+ *                              cutoff in f32, bin = (uint32_t)(d * s), counted iff d * s < nbins (a pair at exactly d == cutoff is in
+ *                              the list but may fall outside).  nbins 1 .. 4096, else GR_E_INVALID_ARG.  Integer adds only: exact.
+ *   gr_contacts_sizes          atoms in the two snapshots
+ *   gr_contacts_set_piece_frames a segment is worked in pieces of frames so that the key, rank and sorted-atom workspace stays within
+ *                              256 MiB (one frame where that alone is larger); n forces pieces of n frames, 0 restores the default.
+ *                              The result never depends on it.
+ *   gr_contacts_stat           GR_CT_STAT_LAST_LAUNCHES / _LAST_PIECES: kernel launches / pieces of the last call; _LAST_TOTAL: pairs of
+ *                              the last pairs call; GR_CT_STAT_TILE: candidates that one workgroup stages in LDS at once (512)
+ * Per piece a fixed number of launches: a counting sort of both groups into the cells of every frame's own grid (one key space for the
+ * piece), a count walk, a scan, and the write walk.  The walk works per run of query cells adjacent along x: their candidates are staged
+ * once in LDS and ordered by atom index there, a team of lanes shares a query and places its hits by ballot and popcount.  No atomic
+ * decides a position or a count, so the lists are the same bits whatever the batch, the piece size, the neighbours or the run. */
+enum { GR_CT_STAT_LAST_LAUNCHES = 1, GR_CT_STAT_LAST_PIECES = 2, GR_CT_STAT_LAST_TOTAL = 3, GR_CT_STAT_TILE = 4 };
+gr_contacts *gr_contacts_create(gr_ctx *ctx, const char *group1, const char *group2, float cutoff, int *status);
+void gr_contacts_destroy(gr_contacts *ct);
+int gr_contacts_pairs_batch(gr_contacts *ct, uint32_t first_slot, uint32_t n_frames, uint64_t max_pairs,
+                            uint64_t *n_pairs /* [n_frames] or NULL */, uint64_t *n_total /* or NULL */, int *status_out /* [n_frames] or NULL */);
+int gr_contacts_read(gr_contacts *ct, uint64_t *offsets /* [n_frames + 1] or NULL */, uint32_t *i, uint32_t *j, float *d, uint64_t cap, uint64_t *n_total);
+int gr_contacts_read_device(gr_contacts *ct, const uint32_t **i_dev, const uint32_t **j_dev, const float **d_dev,
+                            const uint64_t **offsets_dev, uint64_t *n_frames, uint64_t *n_total);
+int gr_contacts_count_batch(gr_contacts *ct, uint32_t first_slot, uint32_t n_frames,
+                            uint32_t *per_atom /* [n_frames][n1] or NULL */, uint64_t *n_pairs /* [n_frames] or NULL */, int *status_out);
+int gr_contacts_hist_batch(gr_contacts *ct, uint32_t first_slot, uint32_t n_frames, uint32_t nbins,
+                           uint64_t *hist /* [n_frames][nbins] */, int *status_out);
+int gr_contacts_sizes(const gr_contacts *ct, uint64_t *n1, uint64_t *n2);
+int gr_contacts_set_piece_frames(gr_contacts *ct, uint32_t n);      /* 0: default; the result never depends on it */
+int gr_contacts_stat(const gr_contacts *ct, int key, uint64_t *value);
 
 /* ---------------------------------------------------------------- xtc reader (host side)
  * The stage in front of the path: XtcReader (src/io/xtc_io/mod.rs, molly_xtc.rs:96-308, xdrfile_xtc.rs:42-104).

@@ -888,4 +888,84 @@ class Region {
     gr_region *rg_ = nullptr;
 };
 
+// ---- Contacts: all pairs (i in group1, j in group2, i != j) within a cut-off, for every frame of a block of resident frames, in one call
+// (the loop over CellGrid::new + neighbors_iter + distance filter of each frame: cellgrid.rs:301-409, hbonds.rs:248-265)
+class Contacts {
+  public:
+    struct Lists { std::vector<uint64_t> offsets; std::vector<uint32_t> i, j; std::vector<float> d; };
+
+    Contacts(System &system, const std::string &group1, const std::string &group2, float cutoff) : ctx_(system.raw()) {
+        int st = 0;
+        ct_ = gr_contacts_create(ctx_, group1.c_str(), group2.c_str(), cutoff, &st);
+        if (!ct_) raise(st);
+        gr_contacts_sizes(ct_, &n1_, &n2_);
+    }
+    ~Contacts() { if (ct_) gr_contacts_destroy(ct_); }
+    Contacts(const Contacts &) = delete;
+    Contacts &operator=(const Contacts &) = delete;
+    Contacts(Contacts &&o) noexcept : ctx_(o.ctx_), ct_(o.ct_), n1_(o.n1_), n2_(o.n2_) { o.ct_ = nullptr; }
+
+    uint64_t n1() const { return n1_; }
+    uint64_t n2() const { return n2_; }
+    // searches n_frames slots from first_slot; the lists stay on the device -> the frames' pair counts (0 for a failed frame).  When the
+    // total exceeds max_pairs the call only counts.  A failed frame throws the first failure unless `status` is given
+    std::vector<uint64_t> pairs(uint32_t first_slot, uint32_t n_frames, uint64_t max_pairs = UINT64_MAX, std::vector<int> *status = nullptr) {
+        std::vector<uint64_t> counts(n_frames);
+        std::vector<int> st(n_frames);
+        const int r = gr_contacts_pairs_batch(ct_, first_slot, n_frames, max_pairs, counts.data(), nullptr, st.data());
+        if (status) *status = st;
+        else if (r != GR_OK) raise(r);
+        return counts;
+    }
+    // the last pairs call: offsets[n_frames + 1] and (i, j, d), frame after frame
+    Lists lists() {
+        uint64_t nf = 0, total = 0;
+        gr_contacts_read_device(ct_, nullptr, nullptr, nullptr, nullptr, &nf, &total);
+        Lists l;
+        l.offsets.assign(nf + 1, 0); l.i.resize(total + 1); l.j.resize(total + 1); l.d.resize(total + 1);
+        const int st = gr_contacts_read(ct_, l.offsets.data(), l.i.data(), l.j.data(), l.d.data(), total, nullptr);
+        if (st != GR_OK) raise(st);
+        l.i.resize(total); l.j.resize(total); l.d.resize(total);
+        return l;
+    }
+    // per_atom[f * n1 + k] = pairs of the k-th atom of group1 in frame f; n_pairs (when given) their sums
+    std::vector<uint32_t> counts(uint32_t first_slot, uint32_t n_frames, std::vector<uint64_t> *n_pairs = nullptr, std::vector<int> *status = nullptr) {
+        std::vector<uint32_t> per_atom((size_t)n_frames * n1_ + 1);
+        std::vector<uint64_t> np(n_frames);
+        std::vector<int> st(n_frames);
+        const int r = gr_contacts_count_batch(ct_, first_slot, n_frames, per_atom.data(), np.data(), st.data());
+        if (n_pairs) *n_pairs = np;
+        if (status) *status = st;
+        else if (r != GR_OK) raise(r);
+        per_atom.resize((size_t)n_frames * n1_);
+        return per_atom;
+    }
+    // hist[f * nbins + b] over [0, cutoff)
+    std::vector<uint64_t> hist(uint32_t first_slot, uint32_t n_frames, uint32_t nbins, std::vector<int> *status = nullptr) {
+        std::vector<uint64_t> h((size_t)n_frames * nbins + 1);
+        std::vector<int> st(n_frames);
+        const int r = gr_contacts_hist_batch(ct_, first_slot, n_frames, nbins, h.data(), st.data());
+        if (status && r != GR_E_INVALID_ARG) *status = st;
+        else if (r != GR_OK) raise(r);
+        h.resize((size_t)n_frames * nbins);
+        return h;
+    }
+    void set_piece_frames(uint32_t n) { gr_contacts_set_piece_frames(ct_, n); }
+    uint64_t stat(int key) const { uint64_t v = 0; if (gr_contacts_stat(ct_, key, &v) != GR_OK) throw std::invalid_argument("Contacts::stat | unknown key"); return v; }
+    gr_contacts *raw() const { return ct_; }
+
+  private:
+    [[noreturn]] void raise(int st) const {
+        switch (st) {
+        case GR_E_GROUP_NOT_FOUND: throw Error("GroupError", "NotFound", st);
+        case GR_E_NO_POSITION: throw Error("GroupError", "InvalidPosition", st, gr_last_error_index(ctx_));
+        case GR_E_NO_BOX: case GR_E_NOT_ORTHOGONAL: case GR_E_ZERO_BOX: throw Error("GroupError", "InvalidSimBox(" + simbox_variant(st) + ")", st);
+        default: throw Error("DeviceError", std::string(gr_status_string(st)) + ": " + gr_last_error(ctx_), st);
+        }
+    }
+    gr_ctx *ctx_ = nullptr;
+    gr_contacts *ct_ = nullptr;
+    uint64_t n1_ = 0, n2_ = 0;
+};
+
 }  // namespace groan

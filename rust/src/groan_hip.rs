@@ -51,11 +51,16 @@ pub const GR_RG_STAT_LAST_LAUNCHES: c_int = 1;
 pub const GR_RG_STAT_LAST_PIECES: c_int = 2;
 pub const GR_RG_STAT_LAST_TOTAL: c_int = 3;
 pub const GR_RG_STAT_CHUNK: c_int = 4;
+pub const GR_CT_STAT_LAST_LAUNCHES: c_int = 1;
+pub const GR_CT_STAT_LAST_PIECES: c_int = 2;
+pub const GR_CT_STAT_LAST_TOTAL: c_int = 3;
+pub const GR_CT_STAT_TILE: c_int = 4;
 
 #[repr(C)] pub struct gr_hbond_plan { _private: [u8; 0] }
 #[repr(C)] pub struct gr_gridmap { _private: [u8; 0] }
 #[repr(C)] pub struct gr_segments { _private: [u8; 0] }
 #[repr(C)] pub struct gr_region { _private: [u8; 0] }
+#[repr(C)] pub struct gr_contacts { _private: [u8; 0] }
 #[repr(C)] pub struct gr_pool { _private: [u8; 0] }
 #[repr(C)] pub struct gr_comm { _private: [u8; 0] }
 /// `body(ctx, worker, frame, user, result)` of gr_pool_map: non-zero return = the frame's error (the first one wins)
@@ -188,6 +193,19 @@ extern "C" {
     pub fn gr_region_group(r: *mut gr_region, frame: u32, name: *const c_char) -> c_int;
     pub fn gr_region_set_piece_frames(r: *mut gr_region, n: u32) -> c_int;
     pub fn gr_region_stat(r: *const gr_region, key: c_int, value: *mut u64) -> c_int;
+    // Contacts: CellGrid::new + neighbors_iter + distance filter for every frame of a block of resident slots
+    pub fn gr_contacts_create(ctx: *mut gr_ctx, group1: *const c_char, group2: *const c_char, cutoff: c_float, status: *mut c_int) -> *mut gr_contacts;
+    pub fn gr_contacts_destroy(ct: *mut gr_contacts);
+    pub fn gr_contacts_pairs_batch(ct: *mut gr_contacts, first_slot: u32, n_frames: u32, max_pairs: u64, n_pairs: *mut u64, n_total: *mut u64,
+                                   status_out: *mut c_int) -> c_int;
+    pub fn gr_contacts_read(ct: *mut gr_contacts, offsets: *mut u64, i: *mut u32, j: *mut u32, d: *mut c_float, cap: u64, n_total: *mut u64) -> c_int;
+    pub fn gr_contacts_read_device(ct: *mut gr_contacts, i_dev: *mut *const u32, j_dev: *mut *const u32, d_dev: *mut *const c_float,
+                                   offsets_dev: *mut *const u64, n_frames: *mut u64, n_total: *mut u64) -> c_int;
+    pub fn gr_contacts_count_batch(ct: *mut gr_contacts, first_slot: u32, n_frames: u32, per_atom: *mut u32, n_pairs: *mut u64, status_out: *mut c_int) -> c_int;
+    pub fn gr_contacts_hist_batch(ct: *mut gr_contacts, first_slot: u32, n_frames: u32, nbins: u32, hist: *mut u64, status_out: *mut c_int) -> c_int;
+    pub fn gr_contacts_sizes(ct: *const gr_contacts, n1: *mut u64, n2: *mut u64) -> c_int;
+    pub fn gr_contacts_set_piece_frames(ct: *mut gr_contacts, n: u32) -> c_int;
+    pub fn gr_contacts_stat(ct: *const gr_contacts, key: c_int, value: *mut u64) -> c_int;
     pub fn gr_ctx_set_tuning(ctx: *mut gr_ctx, key: c_int, value: i64) -> c_int;   // GR_TUNE_* (include/groan_hip.h)
     pub fn gr_host_alloc(bytes: usize) -> *mut c_void;                              // pinned memory: asynchronous gr_frame_upload
     pub fn gr_host_free(p: *mut c_void);
