@@ -27,6 +27,7 @@ GM_STAT_LDS_LAUNCHES, GM_STAT_GLOBAL_LAUNCHES, GM_STAT_LDS_BUDGET = 1, 2, 3
 SEG_STAT_TEAM4, SEG_STAT_TEAM16, SEG_STAT_WAVE, SEG_STAT_WORKGROUP, SEG_STAT_LAST_LAUNCHES, SEG_STAT_LAST_LAUNCH_SETS = 1, 2, 3, 4, 5, 6
 RG_STAT_LAST_LAUNCHES, RG_STAT_LAST_PIECES, RG_STAT_LAST_TOTAL, RG_STAT_CHUNK = 1, 2, 3, 4
 CT_STAT_LAST_LAUNCHES, CT_STAT_LAST_PIECES, CT_STAT_LAST_TOTAL, CT_STAT_TILE = 1, 2, 3, 4
+CT_STAT_LAST_RUNS, CT_STAT_LAST_CELLS, CT_STAT_LAST_RUN_CELLS_MIN, CT_STAT_LAST_RUN_CELLS_MAX, CT_STAT_LAST_WALK_GROUPS = 5, 6, 7, 8, 9
 CT_MAX_BINS = 4096
 MAX_SHAPES = 8
 
@@ -180,6 +181,7 @@ SIGNATURES = {
     "gr_contacts_hist_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "gr_contacts_sizes": (C.c_int, [C.c_void_p, c_u64p, c_u64p]),
     "gr_contacts_set_piece_frames": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "gr_contacts_set_walk_groups": (C.c_int, [C.c_void_p, C.c_uint32]),
     "gr_contacts_stat": (C.c_int, [C.c_void_p, C.c_int, c_u64p]),
     "gr_group_center_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "gr_group_translate_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_void_p, C.c_void_p]),

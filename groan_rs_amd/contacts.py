@@ -143,6 +143,10 @@ class Contacts:
         """frames per piece of the sort workspace (0: the default); the result does not depend on it"""
         self._lib.gr_contacts_set_piece_frames(self._ct, int(n))
 
+    def set_walk_groups(self, n):
+        """workgroups of a walk launch, at most (0: the default); the result does not depend on it"""
+        self._lib.gr_contacts_set_walk_groups(self._ct, int(n))
+
     def stat(self, key):
         v = C.c_uint64(0)
         if self._lib.gr_contacts_stat(self._ct, int(key), C.byref(v)) != OK:

@@ -66,6 +66,7 @@ struct gr_contacts {
     std::vector<uint32_t> atoms1, atoms2;                    // the snapshot, group order
     grbuf::Dev<uint32_t> atoms_dev;                          // [n1 + n2]
     uint32_t piece_frames = 0;                               // 0: by GR_CT_WS_BYTES
+    uint32_t walk_groups = 0;                                // 0: GR_CT_MAX_WG
     grbuf::Dev<unsigned char> ws;                            // the piece's workspace
     grbuf::Pinned<unsigned char> hbuf;                       // frames up, offsets + error words down
     grbuf::Dev<uint32_t> li[2], lj[2]; grbuf::Dev<float> ld[2]; int cur = 0;   // the lists: [cur]; the other set is where they move to grow
@@ -74,6 +75,7 @@ struct gr_contacts {
     uint64_t n_frames = 0, total = 0;                        // the last pairs call's result (0 frames after a failed call)
     bool have_lists = false;                                 // false: count only (the total exceeded max_pairs)
     uint64_t last_launches = 0, last_pieces = 0;
+    uint64_t last_runs = 0, last_cells = 0, last_rx_min = 0, last_rx_max = 0, last_walk_groups = 0;   // over the frames that passed their host checks
 };
 
 namespace {
@@ -368,6 +370,7 @@ int ct_run(gr_contacts *ct, int mode, uint32_t first_slot, uint32_t n_frames, ui
     const bool pairs = mode == GR_CT_WRITE;
     if (pairs) { ct->n_frames = 0; ct->total = 0; ct->have_lists = false; }
     ct->last_launches = 0; ct->last_pieces = 0;
+    ct->last_runs = 0; ct->last_cells = 0; ct->last_rx_min = 0; ct->last_rx_max = 0; ct->last_walk_groups = 0;
     int st = slot_check(c, first_slot, n_frames); if (st) return st;
     if (mode == GR_CT_HIST && (nbins == 0 || nbins > GR_CT_MAX_BINS)) return fail(c, GR_E_INVALID_ARG, "histogram: 1 .. 4096 bins over (0, cutoff)");
     if (mode == GR_CT_HIST && !hist) return fail(c, GR_E_INVALID_ARG, "hist is NULL");
@@ -405,6 +408,9 @@ int ct_run(gr_contacts *ct, int mode, uint32_t first_slot, uint32_t n_frames, ui
                     F.g = ct_grid(c->boxes_host[s0 + p0 + f], ct->cutoff, cells_cap);
                     F.rx = ct_run_cells(ct, F.g); F.ok = 1;
                     nkeys += F.g.ncells;
+                    ct->last_cells += F.g.ncells;
+                    ct->last_rx_min = ct->last_rx_max ? std::min<uint64_t>(ct->last_rx_min, F.rx) : F.rx;
+                    ct->last_rx_max = std::max<uint64_t>(ct->last_rx_max, F.rx);
                     n_units += (uint64_t)F.g.nc[2] * F.g.nc[1] * ((F.g.nc[0] + F.rx - 1u) / F.rx);
                 }
                 const uint64_t n_el = (uint64_t)np * per, n_t = (uint64_t)np * n1, n_keys_all = nkeys * tables;
@@ -412,6 +418,7 @@ int ct_run(gr_contacts *ct, int mode, uint32_t first_slot, uint32_t n_frames, ui
                     return fail(c, GR_E_INVALID_ARG, "contacts: the piece is too large (gr_contacts_set_piece_frames)");
                 ++ct->last_pieces;
                 if (n_units == 0) continue;                  // every frame of the piece failed its checks
+                ct->last_runs += n_units;
                 // workspace
                 size_t tmp_cells = 0, tmp_q = 0;
                 (void)rocprim::exclusive_scan(nullptr, tmp_cells, (uint32_t *)nullptr, (uint32_t *)nullptr, 0u, (size_t)n_keys_all + 1, rocprim::plus<uint32_t>(), c->stream);
@@ -435,7 +442,8 @@ int ct_run(gr_contacts *ct, int mode, uint32_t first_slot, uint32_t n_frames, ui
                 const GrBox *boxes = c->boxes_dev + s0 + p0;
                 const uint32_t table1 = ct->same ? 0u : (uint32_t)nkeys;
                 auto blocks = [](uint64_t n) { return dim3((uint32_t)((n + 255) / 256)); };
-                const dim3 walk_grid((uint32_t)std::min<uint64_t>(n_units, GR_CT_MAX_WG));
+                const dim3 walk_grid((uint32_t)std::min<uint64_t>(n_units, ct->walk_groups ? ct->walk_groups : GR_CT_MAX_WG));
+                ct->last_walk_groups = std::max<uint64_t>(ct->last_walk_groups, walk_grid.x);
                 HIPCHK(c, hipMemcpyAsync(fr_d, fr_h, sizeof(GrCtFrame) * np, hipMemcpyHostToDevice, c->stream));
                 HIPCHK(c, hipMemsetAsync(cell_count, 0, 4 * (n_keys_all + 1), c->stream));
                 HIPCHK(c, hipMemsetAsync(bad, 0xFF, 8 * (size_t)np, c->stream));
@@ -612,6 +620,12 @@ int gr_contacts_set_piece_frames(gr_contacts *ct, uint32_t n) try {
     return GR_OK;
 } catch (...) { return gr_abi_guard(); }
 
+int gr_contacts_set_walk_groups(gr_contacts *ct, uint32_t n) try {
+    if (!ct) return GR_E_INVALID_ARG;
+    ct->walk_groups = n;
+    return GR_OK;
+} catch (...) { return gr_abi_guard(); }
+
 int gr_contacts_stat(const gr_contacts *ct, int key, uint64_t *value) try {
     if (!ct || !value) return GR_E_INVALID_ARG;
     switch (key) {
@@ -619,6 +633,11 @@ int gr_contacts_stat(const gr_contacts *ct, int key, uint64_t *value) try {
     case GR_CT_STAT_LAST_PIECES: *value = ct->last_pieces; return GR_OK;
     case GR_CT_STAT_LAST_TOTAL: *value = ct->total; return GR_OK;
     case GR_CT_STAT_TILE: *value = GR_CT_TILE; return GR_OK;
+    case GR_CT_STAT_LAST_RUNS: *value = ct->last_runs; return GR_OK;
+    case GR_CT_STAT_LAST_CELLS: *value = ct->last_cells; return GR_OK;
+    case GR_CT_STAT_LAST_RUN_CELLS_MIN: *value = ct->last_rx_min; return GR_OK;
+    case GR_CT_STAT_LAST_RUN_CELLS_MAX: *value = ct->last_rx_max; return GR_OK;
+    case GR_CT_STAT_LAST_WALK_GROUPS: *value = ct->last_walk_groups; return GR_OK;
     default: return GR_E_INVALID_ARG;
     }
 } catch (...) { return gr_abi_guard(); }

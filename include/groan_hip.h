@@ -757,12 +757,18 @@ int gr_region_stat(const gr_region *r, int key, uint64_t *value);
  *                              256 MiB (one frame where that alone is larger); n forces pieces of n frames, 0 restores the default.
  *                              The result never depends on it.
  *   gr_contacts_stat           GR_CT_STAT_LAST_LAUNCHES / _LAST_PIECES: kernel launches / pieces of the last call; _LAST_TOTAL: pairs of
- *                              the last pairs call; GR_CT_STAT_TILE: candidates that one workgroup stages in LDS at once (512)
+ *                              the last pairs call; GR_CT_STAT_TILE: candidates that one workgroup stages in LDS at once (512).
+ *                              Over the frames of the last call that passed their host checks: _LAST_RUNS: runs of query cells walked;
+ *                              _LAST_CELLS: cells of their grids; _LAST_RUN_CELLS_MIN / _MAX: fewest / most query cells per run;
+ *                              _LAST_WALK_GROUPS: the largest grid of a walk launch
+ *   gr_contacts_set_walk_groups caps the workgroups of a walk launch: min(runs of the piece, n), 0 restores the default (8192).  A
+ *                              workgroup then serves several runs, and frames, in turn.  For tests; the result never depends on it.
  * Per piece a fixed number of launches: a counting sort of both groups into the cells of every frame's own grid (one key space for the
  * piece), a count walk, a scan, and the write walk.  The walk works per run of query cells adjacent along x: their candidates are staged
  * once in LDS and ordered by atom index there, a team of lanes shares a query and places its hits by ballot and popcount.  No atomic
  * decides a position or a count, so the lists are the same bits whatever the batch, the piece size, the neighbours or the run. */
-enum { GR_CT_STAT_LAST_LAUNCHES = 1, GR_CT_STAT_LAST_PIECES = 2, GR_CT_STAT_LAST_TOTAL = 3, GR_CT_STAT_TILE = 4 };
+enum { GR_CT_STAT_LAST_LAUNCHES = 1, GR_CT_STAT_LAST_PIECES = 2, GR_CT_STAT_LAST_TOTAL = 3, GR_CT_STAT_TILE = 4, GR_CT_STAT_LAST_RUNS = 5,
+       GR_CT_STAT_LAST_CELLS = 6, GR_CT_STAT_LAST_RUN_CELLS_MIN = 7, GR_CT_STAT_LAST_RUN_CELLS_MAX = 8, GR_CT_STAT_LAST_WALK_GROUPS = 9 };
 gr_contacts *gr_contacts_create(gr_ctx *ctx, const char *group1, const char *group2, float cutoff, int *status);
 void gr_contacts_destroy(gr_contacts *ct);
 int gr_contacts_pairs_batch(gr_contacts *ct, uint32_t first_slot, uint32_t n_frames, uint64_t max_pairs,
@@ -776,6 +782,7 @@ int gr_contacts_hist_batch(gr_contacts *ct, uint32_t first_slot, uint32_t n_fram
                            uint64_t *hist /* [n_frames][nbins] */, int *status_out);
 int gr_contacts_sizes(const gr_contacts *ct, uint64_t *n1, uint64_t *n2);
 int gr_contacts_set_piece_frames(gr_contacts *ct, uint32_t n);      /* 0: default; the result never depends on it */
+int gr_contacts_set_walk_groups(gr_contacts *ct, uint32_t n);       /* 0: default; the result never depends on it */
 int gr_contacts_stat(const gr_contacts *ct, int key, uint64_t *value);
 
 /* ---------------------------------------------------------------- xtc reader (host side)

@@ -951,6 +951,7 @@ class Contacts {
         return h;
     }
     void set_piece_frames(uint32_t n) { gr_contacts_set_piece_frames(ct_, n); }
+    void set_walk_groups(uint32_t n) { gr_contacts_set_walk_groups(ct_, n); }
     uint64_t stat(int key) const { uint64_t v = 0; if (gr_contacts_stat(ct_, key, &v) != GR_OK) throw std::invalid_argument("Contacts::stat | unknown key"); return v; }
     gr_contacts *raw() const { return ct_; }
 

@@ -55,6 +55,11 @@ pub const GR_CT_STAT_LAST_LAUNCHES: c_int = 1;
 pub const GR_CT_STAT_LAST_PIECES: c_int = 2;
 pub const GR_CT_STAT_LAST_TOTAL: c_int = 3;
 pub const GR_CT_STAT_TILE: c_int = 4;
+pub const GR_CT_STAT_LAST_RUNS: c_int = 5;
+pub const GR_CT_STAT_LAST_CELLS: c_int = 6;
+pub const GR_CT_STAT_LAST_RUN_CELLS_MIN: c_int = 7;
+pub const GR_CT_STAT_LAST_RUN_CELLS_MAX: c_int = 8;
+pub const GR_CT_STAT_LAST_WALK_GROUPS: c_int = 9;
 
 #[repr(C)] pub struct gr_hbond_plan { _private: [u8; 0] }
 #[repr(C)] pub struct gr_gridmap { _private: [u8; 0] }
@@ -205,6 +210,7 @@ extern "C" {
     pub fn gr_contacts_hist_batch(ct: *mut gr_contacts, first_slot: u32, n_frames: u32, nbins: u32, hist: *mut u64, status_out: *mut c_int) -> c_int;
     pub fn gr_contacts_sizes(ct: *const gr_contacts, n1: *mut u64, n2: *mut u64) -> c_int;
     pub fn gr_contacts_set_piece_frames(ct: *mut gr_contacts, n: u32) -> c_int;
+    pub fn gr_contacts_set_walk_groups(ct: *mut gr_contacts, n: u32) -> c_int;
     pub fn gr_contacts_stat(ct: *const gr_contacts, key: c_int, value: *mut u64) -> c_int;
     pub fn gr_ctx_set_tuning(ctx: *mut gr_ctx, key: c_int, value: i64) -> c_int;   // GR_TUNE_* (include/groan_hip.h)
     pub fn gr_host_alloc(bytes: usize) -> *mut c_void;                              // pinned memory: asynchronous gr_frame_upload

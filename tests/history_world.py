@@ -36,6 +36,9 @@ RANGES = {"all": (0, N - 1), "small": SMALL, "big": (1003, 6002), "a40": (10, 49
 DEFAULT_TUNING = dict(resident=1, center_resident=1, fuse=1, two_pass=1, small_calls=4096, pairdist_symmetric=1, masked_selections=1, translate_rows=1,
                       xtc_device_encode=1)
 N_XTC = 6
+CT_CUTOFF, CT_BINS = 0.3, 40
+REGION_SPECS = [dict(kind="sphere", position=[2.6, 2.8, 2.2], radius=1.6),                       # a sphere and a cylinder along z, both inside the filled part of the cell
+                dict(kind="cylinder", position=[2.4, 2.6, 0.8], radius=1.2, height=3.0, orientation="z")]
 NAIVE, ESTIMATE, PBC = 0, 1, 2
 CENTRES = [(NAIVE, 0), (NAIVE, 1), (ESTIMATE, 0), (ESTIMATE, 1), (PBC, 0), (PBC, 1)]
 
@@ -134,6 +137,9 @@ class World:
         self.seg = {"mol": G.Segments.from_molecules(self.s), "resid": G.Segments.by_resid(self.s, h["resid"])}
         self.hb = G.HBondAnalysis(self.s, [G.HBondChain("oxy", "oxy", "hyd")], [(0, 0)], HB_DISTANCE, HB_ANGLE, h["bonds"])
         self.map = G.GridMap(self.s, (0.0, 6.0), (0.0, 6.4), (0.25, 0.25))
+        self.ct = G.Contacts(self.s, "oxy", "hyd", CT_CUTOFF)
+        self.region = G.Region(self.s, [G.Sphere(s["position"], s["radius"]) if s["kind"] == "sphere" else
+                                        G.Cylinder(s["position"], s["radius"], s["height"], G.Dimension[s["orientation"].upper()]) for s in REGION_SPECS])
         # the trajectories the readers read: written by the host writers
         self.xtc_path, self.trr_path = os.path.join(self.tmp, "world.xtc"), os.path.join(self.tmp, "world.trr")
         if not os.path.isfile(self.xtc_path):
@@ -488,6 +494,51 @@ def _(w, out):
             w.s.group_remove("geo")
 
 
+def _contacts_lists(w, out):
+    out["off"], out["i"], out["j"], out["d"] = w.ct.lists()
+
+
+@kind("contacts_pairs_8", "pairs", slots=ORTHO8)
+def _(w, out):
+    out["n"], out["st"] = w.ct.pairs(0, 8)
+    _contacts_lists(w, out)
+
+
+@kind("contacts_hist_tric_8", "pairs", slots=TRIC8)
+def _(w, out):
+    out["h"], out["st"] = w.ct.hist(8, 8, CT_BINS)
+
+
+@kind("contacts_counts_1", "pairs", slots=(11,))
+def _(w, out):
+    out["per_atom"], out["n"], out["st"] = w.ct.counts(11, 1)
+
+
+def _region_lists(w, out):
+    out["off"], out["atoms"] = w.region.lists()
+
+
+@kind("region_select_16", "pairs", slots=R16, how="upload")
+def _(w, out):
+    out["n"], out["st"] = w.region.select("all", 0, 16)
+    _region_lists(w, out)
+
+
+@kind("region_anchored_8", "pairs", slots=tuple(range(4, 12)))
+def _(w, out):
+    out["anchors"], out["cst"] = w.s.group_center_batch("small", PBC, 0, 4, 8)      # the shapes are moved by the centre of `small`, frame by frame
+    out["n"], out["st"] = w.region.select("big", 4, 8, anchors=out["anchors"])
+    _region_lists(w, out)
+
+
+@kind("fail_contacts_nan", "pairs", writes=(3,), failing=True)
+def _(w, out):
+    w.need((2, 4, 5), "set_frame")
+    w.load(3, "set_frame", frame=nan_frame(3, NAN_A40))                             # atom 20: a hydrogen, in group 2 of the search
+    out["n"], out["st"] = w.ct.pairs(2, 4, raise_on_error=False)
+    _contacts_lists(w, out)
+
+
 @kind("fail_alldist_skewed", "pairs", slots=(3,), writes=(3,), failing=True)
 def _(w, out):
     w.s.set_box(FLAT, slot=3)
@@ -739,6 +790,7 @@ ADJACENCIES = {
     7: ["hbond_2", "hbond_8", "hbond_1"],
     8: ["whole_mols", "rebond_whole", "whole_mols"],
     9: ["res_fit_3", "plan_rmsd_masked", "res_fit_9", "plan_rmsd_masked", "res_fit_2"],
+    10: ["fail_contacts_nan", "contacts_pairs_8", "region_select_16", "contacts_pairs_8"],
 }
 
 

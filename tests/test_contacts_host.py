@@ -9,7 +9,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ["gr_contacts_count_batch", "gr_contacts_create", "gr_contacts_destroy", "gr_contacts_hist_batch", "gr_contacts_pairs_batch", "gr_contacts_read",
-         "gr_contacts_read_device", "gr_contacts_set_piece_frames", "gr_contacts_sizes", "gr_contacts_stat"]
+         "gr_contacts_read_device", "gr_contacts_set_piece_frames", "gr_contacts_set_walk_groups", "gr_contacts_sizes", "gr_contacts_stat"]
 
 
 def _header_prototypes():
@@ -41,7 +41,9 @@ def test_stat_keys_are_equal_everywhere():
     txt = open(os.path.join(ROOT, "include", "groan_hip.h")).read()
     keys = {m.group(1): int(m.group(2)) for m in re.finditer(r"\bGR_CT_STAT_([A-Z_]+)\s*=\s*(\d+)", txt)}
     assert keys == {"LAST_LAUNCHES": _lib.CT_STAT_LAST_LAUNCHES, "LAST_PIECES": _lib.CT_STAT_LAST_PIECES, "LAST_TOTAL": _lib.CT_STAT_LAST_TOTAL,
-                    "TILE": _lib.CT_STAT_TILE}
+                    "TILE": _lib.CT_STAT_TILE, "LAST_RUNS": _lib.CT_STAT_LAST_RUNS, "LAST_CELLS": _lib.CT_STAT_LAST_CELLS,
+                    "LAST_RUN_CELLS_MIN": _lib.CT_STAT_LAST_RUN_CELLS_MIN, "LAST_RUN_CELLS_MAX": _lib.CT_STAT_LAST_RUN_CELLS_MAX,
+                    "LAST_WALK_GROUPS": _lib.CT_STAT_LAST_WALK_GROUPS}
     rs = open(os.path.join(ROOT, "rust", "src", "groan_hip.rs")).read()
     rkeys = {m.group(1): int(m.group(2)) for m in re.finditer(r"pub\s+const\s+GR_CT_STAT_([A-Z_]+)\s*:\s*c_int\s*=\s*(\d+)", rs)}
     assert rkeys == keys
@@ -52,7 +54,7 @@ def test_stat_keys_are_equal_everywhere():
 def test_contacts_is_exported():
     import groan_rs_amd as G
     assert G.Contacts is G.contacts.Contacts and "Contacts" in G.__all__
-    for method in ("pairs", "lists", "frame", "lists_device", "counts", "hist", "set_piece_frames", "stat", "close", "__enter__", "__exit__"):
+    for method in ("pairs", "lists", "frame", "lists_device", "counts", "hist", "set_piece_frames", "set_walk_groups", "stat", "close", "__enter__", "__exit__"):
         assert callable(getattr(G.Contacts, method)), method
 
 

@@ -308,6 +308,37 @@ def _check_pairs(G, fresh, h, aux):
         got = np.concatenate([np.arange(a, b + 1) for a, b in r["blocks%d" % k]]) if len(r["blocks%d" % k]) else np.zeros(0)
         assert len(want) > 10 and np.array_equal(got, want), (k, len(got), len(want))
     assert np.array_equal(r["blocks0"], r["blocks2"])
+    # Contacts: the per-slot call, bit for bit (test_gpu_contacts.py)
+    def slot_pairs(f):
+        return aux.s.group_pairs_within("oxy", "hyd", HW.CT_CUTOFF, slot=f)
+    r = fresh.result["contacts_pairs_8"]
+    assert r["raised"] is None and (r["st"] == 0).all() and r["off"].size == 9 and np.array_equal(np.diff(r["off"]), r["n"])
+    for f in range(8):
+        a, b = int(r["off"][f]), int(r["off"][f + 1])
+        i, j, d = slot_pairs(f)
+        assert i.size >= 2 * HW.N_MOL and np.array_equal(r["i"][a:b], i) and np.array_equal(r["j"][a:b], j) and np.array_equal(r["d"][a:b].view(np.uint32), d.view(np.uint32)), f
+    r = fresh.result["contacts_hist_tric_8"]
+    s = F(HW.CT_BINS) / F(HW.CT_CUTOFF)                                         # bin = (uint32)(d * s), counted iff d * s < nbins (groan_hip.h)
+    for k, f in enumerate(HW.TRIC8):
+        t = (slot_pairs(f)[2] * s).astype(F)
+        want = np.bincount(t[t < F(HW.CT_BINS)].astype(np.uint32), minlength=HW.CT_BINS).astype(np.uint64)
+        assert want.sum() >= 2 * HW.N_MOL and np.array_equal(r["h"][k], want), f
+    r = fresh.result["contacts_counts_1"]
+    i, j, d = slot_pairs(11)
+    assert np.array_equal(r["per_atom"][0], np.bincount(i // 3, minlength=HW.N_MOL).astype(np.uint32)) and int(r["n"][0]) == i.size      # oxygen k is atom 3 k
+    # Region: the geometry selection, frame by frame (test_gpu_region.py)
+    r = fresh.result["region_select_16"]
+    assert r["raised"] is None and (r["st"] == 0).all() and np.array_equal(np.diff(r["off"]), r["n"])
+    for f in range(16):
+        want = O.group_from_geometries(h["frames"][f], _idx("all"), h["boxes"][f], HW.REGION_SPECS)
+        assert len(want) > 100 and np.array_equal(r["atoms"][int(r["off"][f]):int(r["off"][f + 1])], want), (f, int(r["n"][f]), len(want))
+    r = fresh.result["region_anchored_8"]
+    assert r["raised"] is None and (r["st"] == 0).all() and (r["cst"] == 0).all() and r["anchors"].dtype == F
+    for k, f in enumerate(range(4, 12)):
+        assert _lattice_error(r["anchors"][k], O.get_center(h["frames"][f], _idx("small"), h["boxes"][f]), h["boxes"][f]) <= REF_CENTRE, f
+        specs = [dict(sp, position=[float(v) for v in (np.asarray(sp["position"], F) + r["anchors"][k]).astype(F)]) for sp in HW.REGION_SPECS]     # stored + anchor in float32
+        want = O.group_from_geometries(h["frames"][f], _idx("big"), h["boxes"][f], specs)
+        assert len(want) > 100 and np.array_equal(r["atoms"][int(r["off"][k]):int(r["off"][k + 1])], want), (f, int(r["n"][k]), len(want))
 
 
 def _check_topology(G, fresh, h):
@@ -455,6 +486,12 @@ def _check_failures(fresh, h):
     assert r["st"].tolist() == [0, 0, E_NO_BOX, 0, E_NO_POSITION, 0] and np.isnan(r["c"][[2, 4]]).all() and not np.isnan(r["c"][[0, 1, 3, 5]]).any()
     r = fresh.result["fail_reduce_mixed"]
     assert r["st"].tolist() == [0, E_NO_BOX, E_NO_POSITION, 0] and np.array_equal(r["v"][[0, 3]], fresh.result["reduce_hist"]["v"][[0, 3]])
+    r = fresh.result["fail_contacts_nan"]                                              # the failed frame is empty, the others are what they are without it
+    good = fresh.result["contacts_pairs_8"]
+    assert r["raised"] is None and r["st"].tolist() == [0, E_NO_POSITION, 0, 0] and r["n"][1] == 0 and np.array_equal(r["n"][[0, 2, 3]], good["n"][[2, 4, 5]])
+    for k, f in ((0, 2), (2, 4), (3, 5)):
+        for label in ("i", "j", "d"):
+            assert np.array_equal(r[label][int(r["off"][k]):int(r["off"][k + 1])].view(np.uint32), good[label][int(good["off"][f]):int(good["off"][f + 1])].view(np.uint32)), (f, label)
     r = fresh.result["fail_hbond_mixed"]
     assert r["st"].tolist() == [0, E_NO_BOX, E_NO_POSITION] and int(r["offsets"][1]) >= 100 and int(r["offsets"][3]) == int(r["offsets"][1])
     r = fresh.result["masses_changed"]

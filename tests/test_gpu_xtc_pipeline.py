@@ -53,12 +53,14 @@ def test_decode_upload_com_wrap_pipeline(tmp_path):
 
     def decoder():
         while True:
+            b = free_q.get()                                                        # the buffer first, then the frame number: whoever holds a number holds a buffer,
+            if b is None:                                                           # so the frame the main thread waits for is never the one left without (with the
+                return                                                              # number first, the 7 buffers free at a time could all go to later frames: a deadlock)
             with lock:
                 f = next_frame[0]
-                if f >= n_frames:
-                    return
                 next_frame[0] += 1
-            b = free_q.get()
+            if f >= n_frames:
+                return
             _, box, step, tm, _ = x.read_frame(f, out=staging[b][0])
             with cond:
                 ready[f] = (b, box)
@@ -86,6 +88,7 @@ def test_decode_upload_com_wrap_pipeline(tmp_path):
             wrapped_first = sysd.get_positions(slot)
     sysd.sync()
     t_all = time.perf_counter() - t0
+    [free_q.put(None) for _ in ths]                                                 # (the decoders still waiting for a buffer)
     [t.join() for t in ths]
 
     # ---- parity against the oracle on the decoded frames (decode is bit-exact, see tests/test_xtc_decoder.py)

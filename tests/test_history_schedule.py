@@ -16,10 +16,11 @@ REQUIRED = [
     "plan_fit_big_fuse1", "plan_fit_masked_fuse0", "plan_fit_listbig_fuse1", "res_fit_3", "res_fit_9", "res_fit_2", "plan_begin_end",
     "atoms_distance", "alldist_40x50", "alldist_300x400", "alldist_masked_self", "alldist_batch_device_40x50", "reduce_max", "reduce_min_rows", "reduce_count_rows",
     "reduce_hist", "iter_all_distances", "pairs_within", "geometries_small_all_small",
+    "contacts_pairs_8", "contacts_hist_tric_8", "contacts_counts_1", "region_select_16", "region_anchored_8",
     "whole_mols", "whole_group_big", "rebond_whole", "seg_mol_2", "seg_mol_9", "seg_mol_1", "seg_resid_2", "seg_resid_9", "seg_resid_1", "hbond_2", "hbond_8", "hbond_1", "gridmap",
     "xtc_write_4", "xtc_write_12", "xtc_read_small", "xtc_read_full", "xtc_read_masked", "trr_read", "xtc_read_full_again", "xtc_read_small_redefined",
     "fail_translate_nan_small", "fail_com_nan_big", "fail_translate_nan_tail", "fail_center_nobox", "fail_center_batch_mixed", "fail_fit_mixed_fused", "fail_center_nogroup",
-    "fail_alldist_skewed", "fail_xtc_range", "fail_seg_nobox",
+    "fail_alldist_skewed", "fail_contacts_nan", "fail_xtc_range", "fail_seg_nobox",
     "fail_redefined_small_plan", "restored_small_plan", "masses_changed", "tune_small_calls0", "tune_pairsym0", "tune_masked0",
 ]
 
@@ -27,7 +28,7 @@ REQUIRED = [
 def test_the_kinds_the_history_tests_need_exist():
     assert not [k for k in REQUIRED if k not in HW.KINDS]
     assert len(HW.KINDS) >= 100 and set(HW.META) == set(HW.KINDS)
-    assert sorted(HW.ADJACENCIES) == list(range(1, 10)) and all(k in HW.KINDS for a in HW.ADJACENCIES.values() for k in a)
+    assert sorted(HW.ADJACENCIES) == list(range(1, 11)) and all(k in HW.KINDS for a in HW.ADJACENCIES.values() for k in a)
     families = set(m["family"] for m in HW.META.values())
     assert families == {"centres", "rmsd", "pairs", "topology", "io", "redef"}
     for fam in families:                                                   # every family can fail, and fail in more than one way
