@@ -24,6 +24,7 @@ CENTER_NAIVE, CENTER_ESTIMATE, CENTER_PBC = 0, 1, 2
 GM_COUNT, GM_X, GM_Y, GM_Z = 0, 1, 2, 3
 GM_WRAP, GM_FORCE_GLOBAL = 1, 2
 GM_STAT_LDS_LAUNCHES, GM_STAT_GLOBAL_LAUNCHES, GM_STAT_LDS_BUDGET = 1, 2, 3
+GM_STAT_LAST_RANGE_GROUPS, GM_STAT_LAST_FRAME_GROUPS, GM_STAT_LAST_CHECK_GROUPS = 4, 5, 6
 SEG_STAT_TEAM4, SEG_STAT_TEAM16, SEG_STAT_WAVE, SEG_STAT_WORKGROUP, SEG_STAT_LAST_LAUNCHES, SEG_STAT_LAST_LAUNCH_SETS = 1, 2, 3, 4, 5, 6
 RG_STAT_LAST_LAUNCHES, RG_STAT_LAST_PIECES, RG_STAT_LAST_TOTAL, RG_STAT_CHUNK = 1, 2, 3, 4
 CT_STAT_LAST_LAUNCHES, CT_STAT_LAST_PIECES, CT_STAT_LAST_TOTAL, CT_STAT_TILE = 1, 2, 3, 4
@@ -151,6 +152,7 @@ SIGNATURES = {
     "gr_gridmap_destroy": (None, [C.c_void_p]),
     "gr_gridmap_dims": (C.c_int, [C.c_void_p, c_u64p, c_u64p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gr_gridmap_stat": (C.c_int, [C.c_void_p, C.c_int, c_u64p]),
+    "gr_gridmap_set_launch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]),
     "gr_gridmap_clear": (C.c_int, [C.c_void_p]),
     "gr_gridmap_accumulate_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "gr_gridmap_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -10,6 +10,8 @@
 //   x2index / y2index     gridmap.rs:715-724   round((x - span0) / tile) as isize: f32 subtraction, correctly rounded f32 division, round
 //                                              half away from zero, Rust's saturating cast (NaN -> 0, +-inf / huge -> isize MAX / MIN)
 //   index2x / index2y     gridmap.rs:729-738   (index as f32 * tile) + span0, product and sum rounded on their own (never an fma)
+// and the LAUNCH GEOMETRY of a call (gm_launch: ranges of the group x workgroups sharing the frames of a range, the check's grid), which
+// the same driver holds against a second statement of its formulas.
 // The sums are 64-bit INTEGERS of the coordinate in units of 2^-20 nm (q = rint((double)v * 2^20), exact in double for every f32):
 // integer adds commute, so the map is the same bit for bit whatever order the hardware applies the atomics in -- on the LDS and the
 // global path, across calls and across runs.  Capacity of a tile: 2^32 contributions of 2048 nm.
@@ -39,6 +41,10 @@
 #define GR_GM_MAX_TILES (1ull << 26)
 #define GR_GM_Q_SCALE 1048576.0          /* 2^20 quanta per nm */
 #define GR_GM_V_LIMIT 2147483648.0f      /* |v| >= 2^31 nm is not accumulated */
+#define GR_GM_LDS_BYTES (64u * 1024u)     /* LDS budget of a privatised map (DESIGN.md 3.8): 5461 tiles with sums, 16384 count-only */
+#define GR_GM_CU_LDS_BYTES (160u * 1024u) /* LDS of a gfx950 CU */
+#define GR_GM_RANGE_UNITS (1u << 18)      /* units of a workgroup's range at most: the u32 LDS counts of 1024 frames stay below 2^32 */
+#define GR_GM_CHECK_WGS 4096u             /* k_gm_check's grid along x at most */
 
 namespace grg {
 
@@ -106,13 +112,36 @@ inline float gm_mean(int64_t sum_q, uint64_t count) {
     return (float)((double)sum_q * (1.0 / GR_GM_Q_SCALE) / (double)count);
 }
 
+// LAUNCH GEOMETRY of one segment of nb frames.  `units`: what a range is cut from (4-atom groups of a span, or list entries); lds_bytes:
+// the privatised map of a workgroup, 0 on the global path.  By default: enough workgroups to fill the chip (as many per CU as the
+// privatised map leaves room for, 8 at most), each with one range of the group (wx ranges of `per` units) and as many frames of the
+// segment as that allows (fy workgroups walk the frames of a range, frame f by workgroup f mod fy); k_gm_check takes 256 units per
+// workgroup, up to GR_GM_CHECK_WGS workgroups that stride.  range_groups / frame_groups / check_groups (gr_gridmap_set_launch) replace
+// wx / fy and cap check_wgs when they are not 0; a range never exceeds GR_GM_RANGE_UNITS units whatever is asked for.
+struct GmLaunch { uint32_t wx, fy, check_wgs, per; };
+
+inline GmLaunch gm_launch(uint64_t units, uint32_t n_cus, uint64_t lds_bytes, uint32_t nb, uint32_t range_groups, uint32_t frame_groups, uint32_t check_groups) {
+    if (units == 0) units = 1;
+    if (nb == 0) nb = 1;
+    const uint64_t per_cu = lds_bytes ? (GR_GM_CU_LDS_BYTES / lds_bytes < 8 ? GR_GM_CU_LDS_BYTES / lds_bytes : 8) : 8;
+    const uint64_t target = (uint64_t)(n_cus ? n_cus : 1u) * per_cu;
+    const uint64_t tiles256 = (units + 255) / 256, floor_wx = (units + GR_GM_RANGE_UNITS - 1) / GR_GM_RANGE_UNITS;
+    uint64_t wx = range_groups ? (range_groups < units ? range_groups : units) : (tiles256 < target ? tiles256 : target);
+    if (wx < floor_wx) wx = floor_wx;
+    uint64_t fy = frame_groups ? frame_groups : (target / wx ? target / wx : 1);
+    if (fy > nb) fy = nb;
+    uint64_t check = tiles256 < GR_GM_CHECK_WGS ? tiles256 : GR_GM_CHECK_WGS;
+    if (check_groups && check_groups < check) check = check_groups;
+    GmLaunch L;
+    L.wx = (uint32_t)wx; L.fy = (uint32_t)fy; L.check_wgs = (uint32_t)check; L.per = (uint32_t)((units + wx - 1) / wx);
+    return L;
+}
+
 }  // namespace grg
 
 #if defined(__HIPCC__)
 
 #define GR_GM_SKIP 0xFFFFFFFEu            /* verdict word: the frame failed its host checks, no kernel touches it (GR_NOIDX: every atom has a position) */
-#define GR_GM_LDS_BYTES (64u * 1024u)     /* LDS budget of a privatised map (DESIGN.md 3.8): 5461 tiles with sums, 16384 count-only */
-#define GR_GM_CU_LDS_BYTES (160u * 1024u) /* LDS of a gfx950 CU */
 
 struct GrGmDev {
     float x0, tx, y0, ty;                 // span0 and tile size along x and y
@@ -132,6 +161,8 @@ struct gr_gridmap {
     uint32_t *verdict_dev = nullptr, *verdict_host = nullptr;
     float *off_dev = nullptr, *off_host = nullptr;
     uint64_t lds_launches = 0, global_launches = 0;
+    uint32_t range_groups = 0, frame_groups = 0, check_groups = 0;       // gr_gridmap_set_launch; 0: the default
+    uint32_t last_wx = 0, last_fy = 0, last_check = 0;                   // grid of the last segment that was launched
 };
 
 namespace {
@@ -320,15 +351,8 @@ int gm_accumulate(gr_gridmap *m, uint32_t first_slot, uint32_t n_frames, const c
     const uint32_t n_tiles = (uint32_t)(m->nx * m->ny);
     const size_t lds_bytes = (size_t)n_tiles * (value ? 12u : 4u);
     const bool lds = !(flags & GR_GM_FORCE_GLOBAL) && lds_bytes <= GR_GM_LDS_BYTES;
-    // launch geometry: enough workgroups to fill the chip (as many per CU as the privatised map leaves room for, 8 at most), each with
-    // one range of the group and as many frames of the segment as that allows; a range of at most 2^18 units keeps the u32 LDS
-    // counts of 1024 frames below 2^32
+    // launch geometry: grg::gm_launch, per segment
     const uint64_t units = form == 1 ? (uint64_t)sel.n : (uint64_t)(((sel.start + (form == 0 ? sel.n : sel.span) - 1u) >> 2) - (sel.start >> 2)) + 1u;
-    const uint32_t per_cu = lds ? (uint32_t)std::min<size_t>(8, GR_GM_CU_LDS_BYTES / std::max<size_t>(lds_bytes, 1)) : 8u;
-    const uint32_t target = std::max<uint32_t>(c->n_cus, 1u) * per_cu;
-    uint32_t wx = (uint32_t)std::min<uint64_t>((units + 255) / 256, target);
-    wx = std::max<uint32_t>(wx, (uint32_t)((units + (1u << 18) - 1) >> 18));
-    const uint32_t check_wgs = (uint32_t)std::min<uint64_t>((units + 255) / 256, 4096);
     GrGmDev P;
     P.x0 = m->span_x[0]; P.tx = m->tile[0]; P.y0 = m->span_y[0]; P.ty = m->tile[1];
     P.nx = (uint32_t)m->nx; P.ny = (uint32_t)m->ny; P.n_tiles = n_tiles; P.value = value; P.wrap = wrap ? 1 : 0;
@@ -346,12 +370,14 @@ int gm_accumulate(gr_gridmap *m, uint32_t first_slot, uint32_t n_frames, const c
             HIPCHK(c, hipMemcpyAsync(m->verdict_dev, m->verdict_host, nb * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
             if (offset) HIPCHK(c, hipMemcpyAsync(m->off_dev, m->off_host, nb * sizeof(float), hipMemcpyHostToDevice, c->stream));
             HIPCHK(c, hipMemsetAsync(m->nout_dev, 0, nb * sizeof(unsigned long long), c->stream));
-            k_gm_check<<<dim3(check_wgs, nb), dim3(256), 0, c->stream>>>(c->frames, c->frame_stride, s0, sel, form, m->verdict_dev);
-            const uint32_t fy = std::min<uint32_t>(nb, std::max<uint32_t>(1u, target / wx));
+            const grg::GmLaunch L = grg::gm_launch(units, c->n_cus, lds ? lds_bytes : 0, nb, m->range_groups, m->frame_groups, m->check_groups);
+            const uint32_t wx = L.wx, fy = L.fy;
+            k_gm_check<<<dim3(L.check_wgs, nb), dim3(256), 0, c->stream>>>(c->frames, c->frame_stride, s0, sel, form, m->verdict_dev);
             if (lds) k_gm_accumulate<true><<<dim3(wx, fy), dim3(256), lds_bytes, c->stream>>>(c->frames, c->frame_stride, s0, nb, sel, form, c->boxes_dev, P);
             else k_gm_accumulate<false><<<dim3(wx, fy), dim3(256), 0, c->stream>>>(c->frames, c->frame_stride, s0, nb, sel, form, c->boxes_dev, P);
             HIPCHK(c, hipGetLastError());
             if (lds) ++m->lds_launches; else ++m->global_launches;
+            m->last_wx = wx; m->last_fy = fy; m->last_check = L.check_wgs;
             HIPCHK(c, hipMemcpyAsync(m->verdict_host, m->verdict_dev, nb * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipMemcpyAsync(m->nout_host, m->nout_dev, nb * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -424,8 +450,17 @@ int gr_gridmap_stat(const gr_gridmap *m, int key, uint64_t *value) try {
     case GR_GM_STAT_LDS_LAUNCHES: *value = m->lds_launches; return GR_OK;
     case GR_GM_STAT_GLOBAL_LAUNCHES: *value = m->global_launches; return GR_OK;
     case GR_GM_STAT_LDS_BUDGET: *value = GR_GM_LDS_BYTES; return GR_OK;
+    case GR_GM_STAT_LAST_RANGE_GROUPS: *value = m->last_wx; return GR_OK;
+    case GR_GM_STAT_LAST_FRAME_GROUPS: *value = m->last_fy; return GR_OK;
+    case GR_GM_STAT_LAST_CHECK_GROUPS: *value = m->last_check; return GR_OK;
     default: return GR_E_INVALID_ARG;
     }
+} catch (...) { return gr_abi_guard(); }
+
+int gr_gridmap_set_launch(gr_gridmap *m, uint32_t range_groups, uint32_t frame_groups, uint32_t check_groups) try {
+    if (!m) return GR_E_INVALID_ARG;
+    m->range_groups = range_groups; m->frame_groups = frame_groups; m->check_groups = check_groups;
+    return GR_OK;
 } catch (...) { return gr_abi_guard(); }
 
 int gr_gridmap_clear(gr_gridmap *m) try {

@@ -151,6 +151,12 @@ class GridMap(TileGeometry):
             raise ValueError("unknown grid map stat %r" % (key,))
         return int(v.value)
 
+    def set_launch(self, range_groups=0, frame_groups=0, check_groups=0):
+        """cap the grids of a call's launches: ranges of the group, workgroups sharing the frames of a range, workgroups of the
+        position check (0: the default).  The result never depends on it; GM_STAT_LAST_*_GROUPS report what was launched"""
+        if self._lib.gr_gridmap_set_launch(self._map, int(range_groups), int(frame_groups), int(check_groups)) != OK:
+            raise ValueError("set_launch on a closed grid map")
+
     # -- filling
     def _raise(self, status):
         lib, ctx = self._lib, self.system._ctx

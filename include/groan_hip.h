@@ -515,11 +515,18 @@ int gr_make_group_whole_batch(gr_ctx *ctx, uint32_t first_slot, uint32_t n_frame
  *                           A map whose privatised copy fits 64 KiB of LDS (12 bytes per tile, 4 when only counting) is accumulated
  *                           per workgroup in LDS over many frames and flushed once; larger maps, and GR_GM_FORCE_GLOBAL, add to
  *                           global memory directly (gr_gridmap_stat counts the launches of either kind).  Same bits either way.
+ *   gr_gridmap_set_launch   caps the grids of the two launches of a segment (tests aim at the kernels' loops with it): the ranges the
+ *                           group is cut into, min(range_groups, units) -- units: 4-atom groups of the group's span, or its list
+ *                           entries; never fewer than ceil(units / 2^18) --, the workgroups that share the frames of a range,
+ *                           min(frame_groups, frames of the segment), and the workgroups of the position check, min(check_groups, its
+ *                           default).  0 restores the default of that value.  GR_GM_STAT_LAST_RANGE_GROUPS / _FRAME_GROUPS /
+ *                           _CHECK_GROUPS: the grid of the last segment that was launched (0: none yet).
  *   gr_gridmap_read         count, sum_q, mean = (float)((double) sum_q * 2^-20 / (double) count) (NaN where count == 0), each
  *                           [nx * ny], row-major with x the outer index; any may be NULL.  gr_gridmap_clear zeroes the map. */
 enum { GR_GM_COUNT = 0, GR_GM_X = 1, GR_GM_Y = 2, GR_GM_Z = 3 };          /* what is summed per tile besides the count */
 enum { GR_GM_WRAP = 1, GR_GM_FORCE_GLOBAL = 2 };                           /* flags */
-enum { GR_GM_STAT_LDS_LAUNCHES = 1, GR_GM_STAT_GLOBAL_LAUNCHES = 2, GR_GM_STAT_LDS_BUDGET = 3 /* bytes */ };
+enum { GR_GM_STAT_LDS_LAUNCHES = 1, GR_GM_STAT_GLOBAL_LAUNCHES = 2, GR_GM_STAT_LDS_BUDGET = 3 /* bytes */,
+       GR_GM_STAT_LAST_RANGE_GROUPS = 4, GR_GM_STAT_LAST_FRAME_GROUPS = 5, GR_GM_STAT_LAST_CHECK_GROUPS = 6 };
 int gr_gridmap_len(const float span[2], float tile, uint64_t *n);
 int64_t gr_gridmap_coord2index(float span0, float tile, float coord);
 float gr_gridmap_index2coord(float span0, float tile, uint64_t index);
@@ -528,6 +535,7 @@ gr_gridmap *gr_gridmap_from_box(gr_ctx *ctx, uint32_t slot, const float tile_dim
 void gr_gridmap_destroy(gr_gridmap *map);
 int gr_gridmap_dims(const gr_gridmap *map, uint64_t *nx, uint64_t *ny, float span_x[2], float span_y[2], float tile_dim[2]);
 int gr_gridmap_stat(const gr_gridmap *map, int key, uint64_t *value);
+int gr_gridmap_set_launch(gr_gridmap *map, uint32_t range_groups, uint32_t frame_groups, uint32_t check_groups);   /* 0: default; the result never depends on it */
 int gr_gridmap_clear(gr_gridmap *map);
 int gr_gridmap_accumulate_batch(gr_gridmap *map, uint32_t first_slot, uint32_t n_frames, const char *group, int value,
                                 const float *offset /* [n_frames] or NULL */, int flags,

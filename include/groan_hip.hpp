@@ -708,6 +708,9 @@ class GridMap {
         return outside;
     }
     void clear() { const int st = gr_gridmap_clear(map_); if (st != GR_OK) raise(st); }
+    // caps the grids of a call's launches (0: the default); the result never depends on it
+    void set_launch(uint32_t range_groups = 0, uint32_t frame_groups = 0, uint32_t check_groups = 0) { gr_gridmap_set_launch(map_, range_groups, frame_groups, check_groups); }
+    uint64_t stat(int key) const { uint64_t v = 0; if (gr_gridmap_stat(map_, key, &v) != GR_OK) throw std::invalid_argument("GridMap::stat | unknown key"); return v; }
     std::vector<uint64_t> counts() { std::vector<uint64_t> v(n_tiles()); read(v.data(), nullptr, nullptr); return v; }      // row-major, x outer
     std::vector<int64_t> sums_q() { std::vector<int64_t> v(n_tiles()); read(nullptr, v.data(), nullptr); return v; }        // units of 2^-20 nm
     std::vector<float> mean() { std::vector<float> v(n_tiles()); read(nullptr, nullptr, v.data()); return v; }              // NaN where nothing was counted

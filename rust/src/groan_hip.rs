@@ -41,6 +41,12 @@ pub const GR_GM_Y: c_int = 2;
 pub const GR_GM_Z: c_int = 3;
 pub const GR_GM_WRAP: c_int = 1;
 pub const GR_GM_FORCE_GLOBAL: c_int = 2;
+pub const GR_GM_STAT_LDS_LAUNCHES: c_int = 1;
+pub const GR_GM_STAT_GLOBAL_LAUNCHES: c_int = 2;
+pub const GR_GM_STAT_LDS_BUDGET: c_int = 3;
+pub const GR_GM_STAT_LAST_RANGE_GROUPS: c_int = 4;
+pub const GR_GM_STAT_LAST_FRAME_GROUPS: c_int = 5;
+pub const GR_GM_STAT_LAST_CHECK_GROUPS: c_int = 6;
 pub const GR_SEG_STAT_TEAM4: c_int = 1;
 pub const GR_SEG_STAT_TEAM16: c_int = 2;
 pub const GR_SEG_STAT_WAVE: c_int = 3;
@@ -172,6 +178,7 @@ extern "C" {
     pub fn gr_gridmap_destroy(map: *mut gr_gridmap);
     pub fn gr_gridmap_dims(map: *const gr_gridmap, nx: *mut u64, ny: *mut u64, span_x: *mut c_float, span_y: *mut c_float, tile_dim: *mut c_float) -> c_int;
     pub fn gr_gridmap_stat(map: *const gr_gridmap, key: c_int, value: *mut u64) -> c_int;
+    pub fn gr_gridmap_set_launch(map: *mut gr_gridmap, range_groups: u32, frame_groups: u32, check_groups: u32) -> c_int;
     pub fn gr_gridmap_clear(map: *mut gr_gridmap) -> c_int;
     pub fn gr_gridmap_accumulate_batch(map: *mut gr_gridmap, first_slot: u32, n_frames: u32, group: *const c_char, value: c_int, offset: *const c_float,
                                        flags: c_int, n_outside: *mut u64, status_out: *mut c_int) -> c_int;

@@ -72,6 +72,27 @@ def mean(count, sum_q):
     return m
 
 
+def launch(units, n_cus, lds_bytes, nb, range_groups=0, frame_groups=0, check_groups=0):
+    """the grids of one segment, from the header's words (gr_gridmap_set_launch) and DESIGN.md 3.8 -> (wx, fy, check_wgs, per).
+    per_cu workgroups fit a CU beside each other: 8, or fewer when the privatised map of lds_bytes fills the CU's 160 KiB sooner
+    (lds_bytes 0: the global path); target = CUs x per_cu workgroups fill the chip; a range is 256 units or more, 2^18 at most."""
+    per_cu = min(8, (160 * 1024) // lds_bytes) if lds_bytes else 8
+    target = max(n_cus, 1) * per_cu
+    wx = min(range_groups, units) if range_groups else min(-(-units // 256), target)
+    wx = max(wx, -(-units // 2 ** 18))
+    fy = min(frame_groups, nb) if frame_groups else min(nb, max(1, target // wx))
+    check = min(-(-units // 256), 4096)
+    if check_groups:
+        check = min(check, check_groups)
+    return wx, fy, check, -(-units // wx)
+
+
+def units(idx, contiguous_or_masked):
+    """what k_gm_accumulate cuts its ranges from: the 4-atom groups of the span of a block or a masked selection, else list entries"""
+    idx = np.asarray(idx)
+    return int((idx[-1] >> 2) - (idx[0] >> 2) + 1) if contiguous_or_masked else len(idx)
+
+
 class Map:
     def __init__(self, span_x, span_y, tile_dim):
         self.span_x, self.span_y, self.tile = (F(span_x[0]), F(span_x[1])), (F(span_y[0]), F(span_y[1])), (F(tile_dim[0]), F(tile_dim[1]))

@@ -10,7 +10,9 @@ Python helpers built on them (groan_rs_amd.gridmap).  Pinned here, as literals:
   is_inside, get_tile                                                                        :1399-1418
   write, write_column_major   the two output strings                                        :1373, :1393
 and the numpy restatement tests/gridmap_ref.py == the driver on random coordinates, on every half-way point between two tiles with
-its two f32 neighbours, on NaN / +-inf, and on the quantiser's edge values; the C++ mirror of the new calls compiles."""
+its two f32 neighbours, on NaN / +-inf, and on the quantiser's edge values; the C++ mirror of the new calls compiles.
+The launch geometry (grg::gm_launch) is held against its second statement gridmap_ref.launch, with and without gr_gridmap_set_launch's
+overrides; a range of at most 2^18 units -- the bound that keeps the u32 LDS counts of 1024 frames below 2^32 -- is pinned only here."""
 import io
 import os
 import subprocess
@@ -51,6 +53,11 @@ int main() {
         }
         else if (op == "coord") { uint32_t s, t; uint64_t i; in >> s >> t; while (in >> i) printf("%u ", ubits(grg::gm_index2coord(i, bits(s), bits(t)))); printf("\n"); }
         else if (op == "quant") { uint32_t v; while (in >> v) { int64_t q = 0; const bool ok = grg::gm_quant(bits(v), q); printf("%d %" PRId64 " ", ok ? 1 : 0, q); } printf("\n"); }
+        else if (op == "launch") {   // units n_cus lds_bytes nb range_groups frame_groups check_groups -> wx fy check_wgs per
+            uint64_t units, lds; uint32_t cus, nb, rg, fg, cg; in >> units >> cus >> lds >> nb >> rg >> fg >> cg;
+            const grg::GmLaunch L = grg::gm_launch(units, cus, lds, nb, rg, fg, cg);
+            printf("%u %u %u %u\n", L.wx, L.fy, L.check_wgs, L.per);
+        }
         else if (op == "mean") { int64_t s; uint64_t c; in >> s >> c; printf("%u\n", ubits(grg::gm_mean(s, c))); }
         else printf("?\n");
     }
@@ -230,12 +237,84 @@ def test_quantiser(driver):
     assert np.isnan(R.mean(np.array([0], np.uint64), np.array([5], np.int64))[0])
 
 
+# ------------------------------------------------------------------ the launch geometry
+CUS, LDS_BYTES, NBS = (0, 1, 256, 304), (0, 12, 11712, 65532, 65536), (1, 12, 1024)
+
+
+def _launch(driver, cases):
+    out = driver(*["launch %d %d %d %d %d %d %d" % c for c in cases])
+    assert len(out) == len(cases)
+    return [tuple(int(v) for v in ln.split()) for ln in out]
+
+
+def _target(n_cus, lds):
+    return max(n_cus, 1) * (min(8, 163840 // lds) if lds else 8)
+
+
+def test_launch_defaults(driver):
+    """no override: the grids the library has always launched, stated a second time in gridmap_ref.launch"""
+    cases = []
+    for cus in CUS:
+        for lds in LDS_BYTES:
+            t = _target(cus, lds)
+            for nb in NBS:
+                for units in (1, 255, 256, 257, 2073, 250000, 2 ** 18 * t - 1, 2 ** 18 * t, 2 ** 18 * t + 1, 2 ** 30):
+                    cases.append((units, cus, lds, nb, 0, 0, 0))
+    got = _launch(driver, cases)
+    for c, (wx, fy, check, per) in zip(cases, got):
+        units, cus, lds, nb = c[:4]
+        assert (wx, fy, check, per) == R.launch(units, cus, lds, nb), c
+        assert wx >= 1 and 1 <= fy <= nb and wx * per >= units, (c, wx, fy, per)           # (trailing ranges may be empty: the kernel clamps u0, u1)
+        assert per <= 2 ** 18, (c, per)                                            # the u32-count bound: 1024 frames x 4 atoms x 2^18 units = 2^30 per tile at most ...
+        assert 1 <= check <= 4096 and check * 256 >= min(units, 4096 * 256)
+    # ... and it binds: beyond 2^18 x target units the floor, not the target, decides the grid
+    t = _target(256, 11712)
+    assert _launch(driver, [(2 ** 18 * t, 256, 11712, 12, 0, 0, 0), (2 ** 18 * t + 1, 256, 11712, 12, 0, 0, 0)]) == [(t, 1, 4096, 2 ** 18), (t + 1, 1, 4096, -(-(2 ** 18 * t + 1) // (t + 1)))]
+    # by hand: the shapes of tests/test_gpu_gridmap_edges.py on 256 CUs (2 workgroups of 65532 B per CU; 8 of 11712 B)
+    assert _launch(driver, [(2073, 256, 65532, 64, 0, 0, 0), (2073, 256, 11712, 12, 0, 0, 0), (1186, 256, 0, 12, 0, 0, 0)]) == [(9, 56, 9, 231), (9, 12, 9, 231), (5, 12, 5, 238)]
+
+
+def test_launch_overrides(driver):
+    cases = []
+    for cus in CUS:
+        for lds in LDS_BYTES:
+            for nb in NBS:
+                for units in (1, 255, 2073, 2 ** 18 + 1, 2 ** 30):
+                    for rg, fg, cg in [(1, 1, 1), (2, 3, 2), (3, 5, 0), (1, 12, 0), (2073, 1, 0), (0, 5, 0), (7, 0, 0), (0, 0, 3), (2 ** 32 - 1, 2 ** 32 - 1, 2 ** 32 - 1)]:
+                        cases.append((units, cus, lds, nb, rg, fg, cg))
+    got = _launch(driver, cases)
+    for c, (wx, fy, check, per) in zip(cases, got):
+        units, cus, lds, nb, rg, fg, cg = c
+        d_wx, d_fy, d_check, _ = R.launch(units, cus, lds, nb)
+        assert (wx, fy, check, per) == R.launch(*c), c
+        floor = -(-units // 2 ** 18)
+        assert wx == (max(min(rg, units), floor) if rg else d_wx), c              # clamped to the units; never below the floor; 0: the default
+        assert fy == (min(fg, nb) if fg else min(nb, max(1, _target(cus, lds) // wx))), c
+        assert check == (min(cg, d_check) if cg else d_check), c
+        assert per == -(-units // wx) and per <= 2 ** 18 and wx * per >= units, c
+    assert _launch(driver, [(100, 256, 12, 12, 1000, 0, 0)])[0][:2] == (100, 12)             # a requested wx larger than the units
+    assert _launch(driver, [(2 ** 18 + 1, 256, 12, 12, 1, 0, 0)])[0][0] == 2                 # the floor stays above the hook
+    assert _launch(driver, [(2073, 256, 12, 12, 1, 99, 0)])[0][:2] == (1, 12)                # frame_groups larger than nb
+    assert _launch(driver, [(2073, 256, 12, 12, 0, 0, 0)])[0] == _launch(driver, [(2073, 256, 12, 12, 9, 12, 9)])[0] == (9, 12, 9, 231)
+
+
+def test_launch_of_the_documented_benchmark(driver):
+    """tools/gridmap_bench.py: 1e6 atoms ("all": 250 000 units), 256 frames per call, a 68 x 51 from_box map with sums, 256 CUs: a workgroup
+    strides through its range (per > 256) and walks several frames (fy < nb) -- both loops run in the documented workload"""
+    (wx, fy, check, per), = _launch(driver, [(250000, 256, 68 * 51 * 12, 256, 0, 0, 0)])
+    assert (wx, fy, check, per) == (768, 1, 977, 326)
+    assert per > 256 and fy < 256
+
+
 def test_status_strings_and_abi(M):
     import groan_rs_amd as g
     lib = g._lib.load()
     assert g._lib.E_INVALID_SPAN == 23 and g._lib.E_INVALID_TILE == 24
     assert lib.gr_status_string(23) == b"invalid span of the grid map" and lib.gr_status_string(24) == b"invalid grid tile"
     assert lib.gr_gridmap_len(None, 1.0, None) == g._lib.E_INVALID_ARG
+    assert lib.gr_gridmap_set_launch(None, 1, 1, 1) == g._lib.E_INVALID_ARG
+    assert (g._lib.GM_STAT_LAST_RANGE_GROUPS, g._lib.GM_STAT_LAST_FRAME_GROUPS, g._lib.GM_STAT_LAST_CHECK_GROUPS) == (4, 5, 6)
+    assert callable(M.GridMap.set_launch)
     assert g.GridMap is M.GridMap and issubclass(M.GridMap, M.TileGeometry)
 
 
@@ -255,9 +334,12 @@ int main() {
     std::vector<float> m = map.mean();
     float tx = 0, ty = 0;
     bool in = map.is_inside(1.0f, 4.0f) && map.get_tile(1.0f, 4.0f, tx, ty);
+    map.set_launch(2, 3, 1);
+    map.set_launch();
+    const uint64_t grid = map.stat(GR_GM_STAT_LAST_RANGE_GROUPS) + map.stat(GR_GM_STAT_LAST_FRAME_GROUPS) + map.stat(GR_GM_STAT_LAST_CHECK_GROUPS);
     map.clear();
     groan::GridMap moved(std::move(box));
-    return (int)(c.size() + s.size() + m.size() + outside.size() + map.n_tiles() + map.n_tiles_x() + map.n_tiles_y()) + (in ? 0 : 1);
+    return (int)(c.size() + s.size() + m.size() + outside.size() + map.n_tiles() + map.n_tiles_x() + map.n_tiles_y() + grid) + (in ? 0 : 1);
 }
 """
 
