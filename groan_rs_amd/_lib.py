@@ -185,6 +185,16 @@ SIGNATURES = {
     "gr_contacts_set_piece_frames": (C.c_int, [C.c_void_p, C.c_uint32]),
     "gr_contacts_set_walk_groups": (C.c_int, [C.c_void_p, C.c_uint32]),
     "gr_contacts_stat": (C.c_int, [C.c_void_p, C.c_int, c_u64p]),
+    "gr_rmsd_panel_create": (C.c_void_p, [C.c_void_p, C.c_char_p, C.c_uint32, c_i32p]),
+    "gr_rmsd_panel_destroy": (None, [C.c_void_p]),
+    "gr_rmsd_panel_append_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "gr_rmsd_panel_clear": (C.c_int, [C.c_void_p]),
+    "gr_rmsd_panel_frames": (C.c_uint32, [C.c_void_p]),
+    "gr_rmsd_panel_n_atoms": (C.c_uint64, [C.c_void_p]),
+    "gr_rmsd_panel_status": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gr_rmsd_panel_set_block_entries": (C.c_int, [C.c_void_p, C.c_uint64]),
+    "gr_rmsd_matrix": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gr_rmsd_matrix_device": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "gr_group_center_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "gr_group_translate_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_void_p, C.c_void_p]),
     "gr_group_wrap_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_void_p]),

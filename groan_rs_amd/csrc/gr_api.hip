@@ -3709,3 +3709,4 @@ int gr_synth_uniform(gr_ctx *c, uint32_t slot, const float *box9, uint64_t seed)
 #include "gr_segments.h" // Segments: per-residue / per-molecule centres of resident frames: partition, kernel and C ABI
 #include "gr_region.h"   // Region: geometry selections over a block of resident frames: kernels, object and C ABI
 #include "gr_contacts.h" // Contacts: cut-off pair search over a block of resident frames: kernels, object and C ABI
+#include "gr_rmsd_panel.h" // RMSDPanel: packed centred frames and their all-pairs RMSD matrix (f64 MFMA product): kernels, object and C ABI

@@ -43,6 +43,7 @@ typedef struct gr_gridmap gr_gridmap;
 typedef struct gr_segments gr_segments;
 typedef struct gr_region gr_region;
 typedef struct gr_contacts gr_contacts;
+typedef struct gr_rmsd_panel gr_rmsd_panel;
 typedef struct gr_xtc gr_xtc;
 
 /* status codes; 1..7 map onto the reference's error enums (src/errors.rs) */
@@ -792,6 +793,53 @@ int gr_contacts_sizes(const gr_contacts *ct, uint64_t *n1, uint64_t *n2);
 int gr_contacts_set_piece_frames(gr_contacts *ct, uint32_t n);      /* 0: default; the result never depends on it */
 int gr_contacts_set_walk_groups(gr_contacts *ct, uint32_t n);       /* 0: default; the result never depends on it */
 int gr_contacts_stat(const gr_contacts *ct, int key, uint64_t *value);
+
+/* ---------------------------------------------------------------- RMSDPanel: the all-pairs RMSD matrix over packed frames
+ * The double loop of System::calc_rmsd(&other, group) (src/system/rmsd.rs:75-166) over a trajectory.  Each side of calc_rmsd is
+ * prepared without its partner (extract_data_from_system :425-446: get_com, shift by box centre - com, wrap; kabsch_rmsd :547-603
+ * subtracts the box centre), so a PANEL keeps, per appended frame, the group's centred coordinates (f32) and G = sum w |x|^2 (f64), and
+ * the slots the frames came from may be overwritten as soon as the append returns: a trajectory far longer than the context's slots
+ * is packed block by block (a 1e4-atom group costs 120 kB per frame).  The matrix of two panels is a dense product in f64
+ * (v_mfma_f64_16x16x4_f64) closed per pair by gr_best_rotation: rmsd^2 = (G_p + G_q - 2 tr(R^T Hw)) / W.  The object keeps a pointer to
+ * its context: destroy it first.
+ *   gr_rmsd_panel_create        snapshots the group's atoms (group order) and their masses; capacity 1 .. 2^20 frames (else
+ *                               GR_E_INVALID_ARG).  GR_E_GROUP_NOT_FOUND, GR_E_EMPTY_GROUP; GR_E_NO_MASS with gr_last_error_index = the
+ *                               first atom of the group without mass, as the RMSD calls report it.
+ *   gr_rmsd_panel_append_batch  packs the n_frames slots from first_slot as the next rows, in one fixed set of launches per 1024-frame
+ *                               segment: the centre stages of gr_group_center_batch(GR_CENTER_PBC, weighted) on the device, then the
+ *                               pack kernel.  Per frame (batch rules below) the status gr_rmsd_batch gives the slot as the current frame:
+ *                               GR_E_NO_BOX, GR_E_NOT_ORTHOGONAL in strict mode, the slot's box status, GR_E_NO_POSITION with the atom's
+ *                               index.  A failed frame still takes a row, marked invalid; status_out[f] is the frame's status and the
+ *                               return value, message and index are the first failed frame's.  Beyond the capacity: GR_E_INVALID_ARG,
+ *                               nothing changes.  GR_E_INVALID_ARG too when the masses of the atoms no longer equal the snapshot.
+ *   gr_rmsd_panel_clear         forgets the rows (the capacity stays)
+ *   gr_rmsd_panel_frames        rows appended so far, failed ones included;  gr_rmsd_panel_n_atoms: atoms of the snapshot
+ *   gr_rmsd_panel_status        the rows' statuses, out[frames]
+ *   gr_rmsd_matrix              out[i][j] (host, [n_rows][n_cols]) = calc_rmsd of row frame i as self against column frame j as
+ *                               reference; NaN when either frame is invalid.  cols == rows is allowed and NULL is shorthand for it: one
+ *                               triangle is computed and mirrored.  Any size: the matrix is worked in column blocks of at most 2^26
+ *                               entries (gr_rmsd_panel_set_block_entries on `rows`: another size, 0 the default; the result never depends on it).
+ *                               GR_E_INVALID_ARG for an empty panel; GR_E_INCONSISTENT_GROUP (counts = n_cols_atoms, n_rows_atoms)
+ *                               when the panels hold different numbers of atoms; GR_E_INVALID_ARG when their mass snapshots are not
+ *                               bit-equal or they live on different devices (different contexts of one device are fine).  THIS NARROWS
+ *                               THE REFERENCE, which would weight with the reference side's masses: with one set of masses G is a
+ *                               constant of the frame, and the RMSD is symmetric in its two frames.
+ *   gr_rmsd_matrix_device       the same, left on the device in the `rows` object (read with gr_device_read) until the next matrix call
+ *                               on that object or its destruction; n_rows x n_cols <= 2^28 entries, else GR_E_INVALID_ARG.
+ * Sums are f64 with exact products, their order depends on the number of atoms alone and no atomic touches them; the closing step
+ * works on a canonical orientation of the pair.  So an entry depends on its two frames (as an unordered pair) and on N alone: not on the
+ * frames' places in their panels, on how they were appended, on their neighbours or on the run; the matrix of a panel with itself is
+ * exactly symmetric. */
+gr_rmsd_panel *gr_rmsd_panel_create(gr_ctx *ctx, const char *group, uint32_t capacity_frames, int *status);
+void gr_rmsd_panel_destroy(gr_rmsd_panel *p);
+int gr_rmsd_panel_append_batch(gr_rmsd_panel *p, uint32_t first_slot, uint32_t n_frames, int *status_out /* [n_frames] or NULL */);
+int gr_rmsd_panel_clear(gr_rmsd_panel *p);
+uint32_t gr_rmsd_panel_frames(const gr_rmsd_panel *p);
+uint64_t gr_rmsd_panel_n_atoms(const gr_rmsd_panel *p);
+int gr_rmsd_panel_status(const gr_rmsd_panel *p, int *out /* [frames] */);
+int gr_rmsd_panel_set_block_entries(gr_rmsd_panel *p, uint64_t n);  /* 0: default; the result never depends on it */
+int gr_rmsd_matrix(gr_rmsd_panel *rows, gr_rmsd_panel *cols /* or NULL */, float *out /* [n_rows][n_cols], host */);
+int gr_rmsd_matrix_device(gr_rmsd_panel *rows, gr_rmsd_panel *cols /* or NULL */, float **out_dev, uint32_t *n_rows, uint32_t *n_cols);
 
 /* ---------------------------------------------------------------- xtc reader (host side)
  * The stage in front of the path: XtcReader (src/io/xtc_io/mod.rs, molly_xtc.rs:96-308, xdrfile_xtc.rs:42-104).

@@ -972,4 +972,64 @@ class Contacts {
     uint64_t n1_ = 0, n2_ = 0;
 };
 
+// ---- RmsdPanel: the centred coordinates of a group for a block of frames, kept after their slots have moved on, and the all-pairs
+// RMSD matrix of two panels (the double loop of System::calc_rmsd, rmsd.rs:75-166, as one f64 product on the matrix cores)
+class RmsdPanel {
+  public:
+    RmsdPanel(System &system, const std::string &group, uint32_t capacity_frames) : ctx_(system.raw()) {
+        int st = 0;
+        p_ = gr_rmsd_panel_create(ctx_, group.c_str(), capacity_frames, &st);
+        if (!p_) raise(st);
+    }
+    ~RmsdPanel() { if (p_) gr_rmsd_panel_destroy(p_); }
+    RmsdPanel(const RmsdPanel &) = delete;
+    RmsdPanel &operator=(const RmsdPanel &) = delete;
+    RmsdPanel(RmsdPanel &&o) noexcept : ctx_(o.ctx_), p_(o.p_) { o.p_ = nullptr; }
+
+    uint32_t frames() const { return gr_rmsd_panel_frames(p_); }
+    uint64_t n_atoms() const { return gr_rmsd_panel_n_atoms(p_); }
+    // packs n_frames slots from first_slot as the next rows -> their statuses; a failed frame throws the first failure unless `status` is given
+    void append(uint32_t first_slot, uint32_t n_frames, std::vector<int> *status = nullptr) {
+        std::vector<int> st(n_frames);
+        const int r = gr_rmsd_panel_append_batch(p_, first_slot, n_frames, st.data());
+        if (status && r != GR_E_INVALID_ARG && r != GR_E_HIP) *status = st;
+        else if (r != GR_OK) raise(r);
+    }
+    void clear() { gr_rmsd_panel_clear(p_); }
+    std::vector<int> status() const { std::vector<int> s(frames() + 1); gr_rmsd_panel_status(p_, s.data()); s.resize(frames()); return s; }
+    // m[i * cols.frames() + j] = calc_rmsd of row frame i (self) against column frame j (reference); NaN where either frame is invalid
+    std::vector<float> matrix(RmsdPanel &cols) {
+        std::vector<float> m((size_t)frames() * cols.frames() + 1);
+        const int st = gr_rmsd_matrix(p_, cols.p_, m.data());
+        if (st != GR_OK) raise(st);
+        m.resize((size_t)frames() * cols.frames());
+        return m;
+    }
+    std::vector<float> matrix() { return matrix(*this); }
+    // the same left on the device (gr_device_read), valid until the next matrix call on this object
+    float *matrix_device(RmsdPanel *cols, uint32_t *n_rows, uint32_t *n_cols) {
+        float *dev = nullptr;
+        const int st = gr_rmsd_matrix_device(p_, cols ? cols->p_ : nullptr, &dev, n_rows, n_cols);
+        if (st != GR_OK) raise(st);
+        return dev;
+    }
+    void set_block_entries(uint64_t n) { gr_rmsd_panel_set_block_entries(p_, n); }
+    gr_rmsd_panel *raw() const { return p_; }
+
+  private:
+    [[noreturn]] void raise(int st) const {
+        switch (st) {
+        case GR_E_GROUP_NOT_FOUND: throw Error("RMSDError", "NonexistentGroup", st);
+        case GR_E_EMPTY_GROUP: throw Error("RMSDError", "EmptyGroup", st);
+        case GR_E_INCONSISTENT_GROUP: throw Error("RMSDError", "InconsistentGroup", st);
+        case GR_E_NO_POSITION: throw Error("RMSDError", "InvalidPosition", st, gr_last_error_index(ctx_));
+        case GR_E_NO_MASS: throw Error("RMSDError", "InvalidMass", st, gr_last_error_index(ctx_));
+        case GR_E_NO_BOX: case GR_E_NOT_ORTHOGONAL: case GR_E_ZERO_BOX: throw Error("RMSDError", "InvalidSimBox(" + simbox_variant(st) + ")", st);
+        default: throw Error("DeviceError", std::string(gr_status_string(st)) + ": " + gr_last_error(ctx_), st);
+        }
+    }
+    gr_ctx *ctx_ = nullptr;
+    gr_rmsd_panel *p_ = nullptr;
+};
+
 }  // namespace groan

@@ -72,6 +72,7 @@ pub const GR_CT_STAT_LAST_WALK_GROUPS: c_int = 9;
 #[repr(C)] pub struct gr_segments { _private: [u8; 0] }
 #[repr(C)] pub struct gr_region { _private: [u8; 0] }
 #[repr(C)] pub struct gr_contacts { _private: [u8; 0] }
+#[repr(C)] pub struct gr_rmsd_panel { _private: [u8; 0] }
 #[repr(C)] pub struct gr_pool { _private: [u8; 0] }
 #[repr(C)] pub struct gr_comm { _private: [u8; 0] }
 /// `body(ctx, worker, frame, user, result)` of gr_pool_map: non-zero return = the frame's error (the first one wins)
@@ -219,6 +220,17 @@ extern "C" {
     pub fn gr_contacts_set_piece_frames(ct: *mut gr_contacts, n: u32) -> c_int;
     pub fn gr_contacts_set_walk_groups(ct: *mut gr_contacts, n: u32) -> c_int;
     pub fn gr_contacts_stat(ct: *const gr_contacts, key: c_int, value: *mut u64) -> c_int;
+    // RMSDPanel: packed centred frames of a group and the all-pairs RMSD matrix of two panels (cols may be null: rows against itself)
+    pub fn gr_rmsd_panel_create(ctx: *mut gr_ctx, group: *const c_char, capacity_frames: u32, status: *mut c_int) -> *mut gr_rmsd_panel;
+    pub fn gr_rmsd_panel_destroy(p: *mut gr_rmsd_panel);
+    pub fn gr_rmsd_panel_append_batch(p: *mut gr_rmsd_panel, first_slot: u32, n_frames: u32, status_out: *mut c_int) -> c_int;
+    pub fn gr_rmsd_panel_clear(p: *mut gr_rmsd_panel) -> c_int;
+    pub fn gr_rmsd_panel_frames(p: *const gr_rmsd_panel) -> u32;
+    pub fn gr_rmsd_panel_n_atoms(p: *const gr_rmsd_panel) -> u64;
+    pub fn gr_rmsd_panel_status(p: *const gr_rmsd_panel, out: *mut c_int) -> c_int;
+    pub fn gr_rmsd_panel_set_block_entries(p: *mut gr_rmsd_panel, n: u64) -> c_int;
+    pub fn gr_rmsd_matrix(rows: *mut gr_rmsd_panel, cols: *mut gr_rmsd_panel, out: *mut c_float) -> c_int;
+    pub fn gr_rmsd_matrix_device(rows: *mut gr_rmsd_panel, cols: *mut gr_rmsd_panel, out_dev: *mut *mut c_float, n_rows: *mut u32, n_cols: *mut u32) -> c_int;
     pub fn gr_ctx_set_tuning(ctx: *mut gr_ctx, key: c_int, value: i64) -> c_int;   // GR_TUNE_* (include/groan_hip.h)
     pub fn gr_host_alloc(bytes: usize) -> *mut c_void;                              // pinned memory: asynchronous gr_frame_upload
     pub fn gr_host_free(p: *mut c_void);
