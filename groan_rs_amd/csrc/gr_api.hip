@@ -81,6 +81,8 @@ struct gr_ctx {
     std::vector<float> masses_host;   // copy kept for plan bookkeeping (weights == masses test)
     GrBox *boxes_dev = nullptr;       // [n_slots]
     GrBox *boxes_host = nullptr;      // pinned [n_slots]
+    uint64_t box_gen = 1;             // bumped by every writer of a boxes_host entry (box_fill, set_boxes_same)
+    struct { uint64_t gen = 0; uint32_t s0 = 0, n = 0; bool same = false; } box_run;   // the last answer of uniform_boxes, good while box_gen stands
     std::vector<int> box_status;      // per slot: GR_OK / GR_E_NO_BOX / GR_E_ZERO_BOX / GR_E_UNSUPPORTED_BOX
     std::vector<uint8_t> box9_set;
     std::vector<float> box9_host;     // [n_slots][9]
@@ -563,6 +565,7 @@ static int slot_box_wait(gr_ctx *c, uint32_t slot) {
 // host half of set_box: boxes_host[slot] + the slot's box status; the caller copies boxes_host to boxes_dev
 void box_fill(gr_ctx *c, uint32_t slot, const float *box9) {
     GrBox &b = c->boxes_host[slot];
+    c->box_gen++;
     if (!box9) {
         gr_box_setup(nullptr, &b);
         c->box_status[slot] = GR_E_NO_BOX; c->box9_set[slot] = 0;
@@ -576,6 +579,17 @@ void box_fill(gr_ctx *c, uint32_t slot, const float *box9) {
         else c->box_status[slot] = GR_OK;
     }
 }
+// the same box in every one of `n` slots from s0 (constant-volume runs): a resident launch then loads the box's constants once.  The answer
+// for a run of slots is remembered until a slot's box is written again (box_gen): calls over frames that stay on the device do not
+// compare n boxes again
+static bool uniform_boxes(gr_ctx *c, uint32_t s0, uint32_t n) {
+    auto &r = c->box_run;
+    if (r.gen == c->box_gen && r.s0 == s0 && r.n == n) return r.same;
+    bool same = true;
+    for (uint32_t f = 1; f < n && same; ++f) same = memcmp(&c->boxes_host[s0 + f], &c->boxes_host[s0], sizeof(GrBox)) == 0;
+    r.gen = c->box_gen; r.s0 = s0; r.n = n; r.same = same;
+    return same;
+}
 int set_box(gr_ctx *c, uint32_t slot, const float *box9, hipStream_t on = nullptr) {
     box_fill(c, slot, box9);
     HIPCHK(c, hipMemcpyAsync(c->boxes_dev + slot, &c->boxes_host[slot], sizeof(GrBox), hipMemcpyHostToDevice, on ? on : c->stream));
@@ -588,6 +602,7 @@ int set_boxes_same(gr_ctx *c, uint32_t first_slot, uint32_t n, const float *box9
     float keep[9];
     if (box9) memcpy(keep, box9, sizeof keep);                 // (box9 may point into box9_host, which the loop below rewrites)
     box_fill(c, first_slot, box9 ? keep : nullptr);
+    c->box_gen++;
     for (uint32_t f = 1; f < n; ++f) {
         const uint32_t s = first_slot + f;
         c->boxes_host[s] = c->boxes_host[first_slot];
@@ -698,8 +713,9 @@ static int res_test_no_start(gr_ctx *c, uint32_t epoch) {
 template <int MODE>
 static int res_close(gr_ctx *c, uint32_t nb, const double *fit_partials, uint32_t nparts, double sum_w, uint32_t epoch, bool fresh, uint32_t *seq) {
     const uint32_t sq = c->res_seq + 1u;
-    k_res_close<MODE><<<dim3(nb), dim3(64), 0, c->stream>>>(fit_partials, nparts, sum_w, c->state_dev, c->res_rec, epoch, fresh ? 1u : 0u, c->res_abort, c->res_closed + nb,
-                                                        c->res_out_dev->st, c->res_out_dev->words, &c->res_out_dev->seq, sq);
+    k_res_close<MODE><<<dim3((nb + GR_RES_CLOSE_WAVES - 1u) / GR_RES_CLOSE_WAVES), dim3(64 * GR_RES_CLOSE_WAVES), 0, c->stream>>>(
+        fit_partials, nparts, sum_w, c->state_dev, c->res_rec, epoch, fresh ? 1u : 0u, c->res_abort, c->res_closed + nb, nb,
+        c->res_out_dev->st, c->res_out_dev->words, &c->res_out_dev->seq, sq);
     HIPCHK(c, hipGetLastError());
     c->res_seq = sq; c->res_closed += nb; *seq = sq;
     return GR_OK;
@@ -1849,8 +1865,7 @@ static int center_resident(gr_ctx *c, uint32_t s0, uint32_t nb, const GrSel &all
     const float *masses = c->masses; GrSel sel_arg = csel; const GrBox *boxes = c->boxes_dev; GrPlanDev plan; memset(&plan, 0, sizeof plan);
     GrFrameState *states = c->state_dev; double *fparts = nullptr;
     void *args[] = { &frames, &stride, &slot0, &nfr, &natoms, &masses, &sel_arg, &boxes, &plan, &states, &fparts, &ctl };
-    bool ubox = true;
-    for (uint32_t f = 1; f < nb && ubox; ++f) ubox = memcmp(&c->boxes_host[s0 + f], &c->boxes_host[s0], sizeof(GrBox)) == 0;
+    const bool ubox = uniform_boxes(c, s0, nb);
     const bool fit_last = c->res_fit_last ? c->res_fit_last == 2 : (uint64_t)res_stream * 10u >= (uint64_t)c->res_max_wgs * 9u;
     { const int sn = res_test_no_start(c, ctl.epoch); if (sn) return sn; }
     if (hipLaunchKernel(resident_center_fn(ubox, fit_last), dim3(res_stream + n_fin), dim3(GrResShape::LANES), args, GrResShape::LDS_BYTES, S) != hipSuccess) {
@@ -2174,19 +2189,26 @@ static int rmsd_exact(gr_rmsd_plan *p, gr_ctx *c, const GrSel &sel, uint32_t fir
 static int segment_begin(gr_rmsd_plan *p, uint32_t s0, uint32_t nb, int fit) {
     gr_ctx *c = p->target;
     Pending &q = p->pend;
-    q = Pending();
+    {   // a fresh Pending that keeps the per-frame vectors' storage from call to call
+        std::vector<int> pre = std::move(q.pre); std::vector<uint64_t> pre_idx = std::move(q.pre_idx); std::vector<std::string> pre_msg = std::move(q.pre_msg);
+        q = Pending();
+        q.pre = std::move(pre); q.pre_idx = std::move(pre_idx); q.pre_msg = std::move(pre_msg);
+    }
     q.s0 = s0; q.nb = nb; q.fit = fit; q.active = true;
     SlotUse use(c, s0, nb);
     const Group *g = find_group(c, p->group.c_str());
-    // host-side checks in the reference's order: box (rmsd.rs:430) -> group exists -> non-empty
-    q.pre.assign(nb, GR_OK); q.pre_idx.assign(nb, 0); q.pre_msg.assign(nb, std::string());
+    // host-side checks in the reference's order: box (rmsd.rs:430) -> group exists -> non-empty.  pre_idx / pre_msg have entries only
+    // in a call with a frame that fails (then for every frame): they are read for failing frames alone
+    q.pre.assign(nb, GR_OK); q.pre_idx.clear(); q.pre_msg.clear();
+    bool all_ok = true;
     for (uint32_t f = 0; f < nb; ++f) {
         int s = box_check(c, s0 + f);
         if (s == GR_OK && !g) s = fail(c, GR_E_GROUP_NOT_FOUND, p->group);
         if (s == GR_OK && g->n == 0) s = fail(c, GR_E_EMPTY_GROUP, p->group);
-        q.pre[f] = s;
-        if (s != GR_OK) { q.pre_msg[f] = c->err; q.pre_idx[f] = c->err_index; }
-        q.any_ok = q.any_ok || s == GR_OK;
+        if (s != GR_OK) {
+            if (all_ok) { q.pre_idx.assign(nb, 0); q.pre_msg.resize(nb); all_ok = false; }
+            q.pre[f] = s; q.pre_msg[f] = c->err; q.pre_idx[f] = c->err_index;
+        } else q.any_ok = true;
     }
     if (!q.any_ok) return GR_OK;
     const GrSel sel = make_sel(*g);
@@ -2223,8 +2245,6 @@ static int segment_begin(gr_rmsd_plan *p, uint32_t s0, uint32_t nb, int fit) {
         // queued (rocprofv3 --hip-trace of bench.py: hipMemcpyAsync 29 us per call), i.e. with the device idle
         // ... and not even that where the resident pass takes the segment: its finalizers start from a fresh state of their own
         // (GrResCtl::fresh_states), so the zeroing waits until the path is known (zero_states)
-        bool all_ok = true;
-        for (uint32_t f = 0; f < nb; ++f) all_ok = all_ok && q.pre[f] == GR_OK;
         states_unset = all_ok;
         if (!all_ok) {
             for (uint32_t f = 0; f < nb; ++f) { GrFrameState z = {}; z.err_index = GR_NOIDX; z.status = q.pre[f]; c->state_host[f] = z; }
@@ -2332,8 +2352,7 @@ static int segment_begin(gr_rmsd_plan *p, uint32_t s0, uint32_t nb, int fit) {
             const float *masses = c->masses; GrSel sel_arg = sel; const GrBox *boxes = c->boxes_dev; GrPlanDev plan = res_msk ? plan_span : p->dev;
             GrFrameState *states = c->state_dev; double *fparts = c->fit_partials.get();
             void *args[] = { &frames, &stride, &slot0, &nfr, &natoms, &masses, &sel_arg, &boxes, &plan, &states, &fparts, &ctl };
-            bool ubox = true;   // the same box in every frame of the segment (constant-volume runs): its constants are loaded once
-            for (uint32_t f = 1; f < nb && ubox; ++f) ubox = memcmp(&c->boxes_host[s0 + f], &c->boxes_host[s0], sizeof(GrBox)) == 0;
+            bool ubox = uniform_boxes(c, s0, nb);   // the same box in every frame of the segment (constant-volume runs): its constants are loaded once
 #ifdef GR_EXP_NO_UBOX
             ubox = false;
 #endif
@@ -2617,7 +2636,12 @@ static int segment_end(gr_rmsd_plan *p, float *rmsd_out, int *status_out, float 
                 c->prof_ms[k] += ms; c->prof_launches[k] += 1; c->prof_frames[k] += nf;
             }
         }
-        std::vector<GrFrameState> res(c->state_host, c->state_host + nb);
+        // the frames' records: c->state_host itself unless a redo below is due -- those overwrite it frame by frame, so they work on a copy
+        bool redo_due = !redo.empty() || q.rmsd_fast || final_states != nullptr;
+        for (uint32_t f = 0; f < nb && !redo_due; ++f) redo_due = c->state_host[f].status == GR_ST_FALLBACK;
+        std::vector<GrFrameState> res_copy;
+        if (redo_due) res_copy.assign(c->state_host, c->state_host + nb);
+        GrFrameState *const res = redo_due ? res_copy.data() : c->state_host;
         if (!redo.empty()) {
             // runs of untouched frames go through the two-pass path as segments of their own (the pass is off meanwhile)
             const int keep = c->resident;
@@ -2702,7 +2726,7 @@ static int segment_end(gr_rmsd_plan *p, float *rmsd_out, int *status_out, float 
             if (rmsd_out) rmsd_out[f] = (s == GR_OK) ? res[f].rmsd : NAN;
             if (R_out) for (int k = 0; k < 9; ++k) R_out[9 * (size_t)f + k] = (s == GR_OK) ? res[f].R[k] : NAN;
         }
-        if (final_states) *final_states = res;
+        if (final_states) *final_states = std::move(res_copy);
     }
     return fe.finish(c);
 }

@@ -89,8 +89,9 @@
 // clock that never runs backwards, the late / waited slot counts run on (the host subtracts what it saw after the launch before)
 // and every streaming wave of a launch that started writes its `progress` word before it leaves.  The epoch is 32 bits: when it
 // wraps the host clears every tagged word and starts again at 1 (res_next_epoch, gr_api.hip).
-// BEHIND the launch one small kernel (k_res_close) adds up the fit sums, hands every frame's closed state and the control words to
-// the host through mapped memory and, last of all, stores the call's sequence number there: the host polls that word.
+// BEHIND the launch one small kernel (k_res_close) adds up the fit sums and closes every frame's state in device memory; its last
+// wave hands all states and the control words to the host through mapped memory and, last of all, stores the call's sequence
+// number there: the host polls that word.
 // Inside a workgroup (no barrier in the loop): a wave writes its record to LDS, RELEASES it with a workgroup-scope fence
 // restricted to the LDS address space (one s_waitcnt lgkmcnt(0); the unrestricted fence would drain the prefetched rows too)
 // and bumps the slot's LDS counter; the wave that later claims the complete frame ACQUIRES with the same kind of fence before it
@@ -1251,47 +1252,103 @@ __global__ __launch_bounds__(GrResShape::LANES) void k_fit_resident(
 #endif
 }
 
-// BEHIND the resident launch, one wave per frame: the frame's fit sums become its rmsd exactly as k_rmsd_close forms it (MODE 0), and the
-// frame's closed state goes to the host through mapped memory (`out_states`, 22 words in one store instruction).  A frame of a launch
-// that started from fresh states (ctl.fresh_states) whose finalizer never ran -- the launch never started, or was aborted before the
-// frame -- has no state of this launch in memory: it is recorded as GR_ST_ABORTED, here and in `state`, which is how the host
-// knows such a frame from one that was closed.  Every wave counts itself on a device word that only counts up (`done_target`: its value
-// when this launch's last wave has arrived); the last one copies the launch's 12 control words and then, released at system scope,
-// stores the call's sequence number: the host polls that word (res_wait, gr_api.hip) -- the contract of the single-wave kernels (gr_small.h).
+// BEHIND the resident launch, one wave per frame (GR_RES_CLOSE_WAVES of them to a workgroup): the frame's fit sums become its rmsd exactly
+// as k_rmsd_close forms it (MODE 0), written into the frame's state in DEVICE memory.  A frame of a launch that started from fresh states
+// (ctl.fresh_states) whose finalizer never ran -- the launch never started, or was aborted before the frame -- has no state of this launch
+// in memory: it is recorded as GR_ST_ABORTED in `state`, which is how the host knows such a frame from one that was closed.  No wave but
+// the last stores to the host or fences at system scope.  The waves of a workgroup meet at a barrier once their stores have been
+// acknowledged; its first wave then counts the workgroup's frames on a device word that only counts up (`done_target`: its value when this
+// launch's last frame has arrived) -- one agent-scope acquire-release add, the release of the workgroup's states.  The wave whose add
+// completes the count has acquired every other workgroup's states through it: it alone copies the launch's `nb` states (agent-scope
+// loads, so a line of its own L2 left from an earlier launch is never taken for one written on another XCD; 16-byte stores) and the 12
+// control words into the mapped block, fences ONCE at system scope and then, released at system scope, stores the call's sequence number:
+// the host polls that word (res_collect, gr_api.hip) -- the contract of the single-wave kernels (gr_small.h).  Every host store thus
+// comes from one wave, in program order, ahead of that wave's own release.
+#ifndef GR_RES_CLOSE_WAVES
+#define GR_RES_CLOSE_WAVES 8       // frames (waves) per workgroup of k_res_close: one cache write-back per workgroup, not per frame (the kernel at 768 frames,
+                                   // traced: 1 -> 27.0 us, 4 -> 14.3, 8 -> 12.8, 16 -> 14.0; profiles/resident_call_path.md)
+#endif
+#define GR_RES_CLOSE_UNROLL 16     // 16-byte pieces per lane and round of the last wave's copy: 32 eight-byte loads in flight per lane
+#define GR_RES_CLOSE_ROUND 32u     // fit sums per lane that are loaded together (a frame of the largest launch has 2048: one round)
 template <int MODE>
-__global__ __launch_bounds__(64) void k_res_close(const double *__restrict__ fit_partials, uint32_t nparts, double sum_w, GrFrameState *state,
+__global__ __launch_bounds__(64 * GR_RES_CLOSE_WAVES) void k_res_close(const double *__restrict__ fit_partials, uint32_t nparts, double sum_w, GrFrameState *state,
                                                   const unsigned long long *__restrict__ rec, uint32_t epoch, uint32_t fresh_states, uint32_t *ctl_words,
-                                                  uint32_t done_target, GrFrameState *out_states, uint32_t *out_words, uint32_t *out_seq, uint32_t seq) {
-    constexpr uint32_t NW = sizeof(GrFrameState) / 4u, W_RMSD = offsetof(GrFrameState, rmsd) / 4u, W_STATUS = offsetof(GrFrameState, status) / 4u;
-    static_assert(sizeof(GrFrameState) % 4u == 0 && NW <= 64u, "a frame state is exported by one wave, a word per lane");
-    const uint32_t frame = blockIdx.x, lane = threadIdx.x;
-    uint32_t *sw = reinterpret_cast<uint32_t *>(state + frame);
-    uint32_t w = 0u;
-    if (fresh_states && (uint32_t)(gr_ld_agent(rec + (size_t)frame * 16u) >> 32) != epoch) {
-        GrFrameState z = {};
-        z.err_index = GR_NOIDX; z.status = GR_ST_ABORTED;
-        if (lane < NW) { w = reinterpret_cast<const uint32_t *>(&z)[lane]; sw[lane] = w; }
-    } else if (lane < NW) w = sw[lane];
-    const int status = __shfl((int)w, (int)W_STATUS, 64);
-    if (MODE == 0 && status == 0) {
-        // four independent chains per lane: the loads of a lane do not wait for one another
-        double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+                                                  uint32_t done_target, uint32_t nb, GrFrameState *__restrict__ out_states, uint32_t *__restrict__ out_words,
+                                                  uint32_t *out_seq, uint32_t seq) {
+    constexpr uint32_t NW = sizeof(GrFrameState) / 4u, W_STATUS = offsetof(GrFrameState, status) / 4u,
+                       W_ERR = offsetof(GrFrameState, err_index) / 4u, WPG = GR_RES_CLOSE_WAVES;
+    static_assert(sizeof(GrFrameState) % 8u == 0 && alignof(GrFrameState) <= 8u && NW <= 64u, "a wave holds a frame state a word per lane; the states are copied in 8-byte words");
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u, frame = blockIdx.x * WPG + wave;
+    if (frame < nb) {
+        // one trip to memory for all a frame needs: its record's tag, its state and (MODE 0) the first round of its fit sums are requested
+        // together, before the tag says whether the state is this launch's and the state whether the sums are wanted
+        constexpr uint32_t RW = GR_RES_CLOSE_ROUND;
+        uint32_t *sw = reinterpret_cast<uint32_t *>(state + frame);
         const double *p = fit_partials + (size_t)frame * nparts;
-        uint32_t k = lane;
-        for (; k + 192 < nparts; k += 256) { s0 += p[k]; s1 += p[k + 64]; s2 += p[k + 128]; s3 += p[k + 192]; }
-        for (; k < nparts; k += 64) s0 += p[k];
-        const double s = gr_wave_sum((s0 + s1) + (s2 + s3));
-        float r = 0.0f;
-        if (lane == 0) { r = (float)sqrt(fmax(s, 0.0) / sum_w); state[frame].rmsd = r; }
-        r = __shfl(r, 0, 64);
-        if (lane == W_RMSD) w = __float_as_uint(r);
+        double v[RW];
+        const unsigned long long tag = fresh_states ? gr_ld_agent(rec + (size_t)frame * 16u) : 0ull;
+        uint32_t w = lane < NW ? sw[lane] : 0u;
+        if (MODE == 0) {
+#pragma unroll
+            for (uint32_t j = 0; j < RW; ++j) v[j] = nparts ? p[min(lane + 64u * j, nparts - 1u)] : 0.0;      // (past the end: the last word again, never added)
+        }
+        if (fresh_states && (uint32_t)(tag >> 32) != epoch) {
+            // (a value-initialised state with err_index = GR_NOIDX and status = GR_ST_ABORTED, word by word from the lane number)
+            w = lane == W_STATUS ? (uint32_t)GR_ST_ABORTED : lane == W_ERR ? GR_NOIDX : 0u;
+            if (lane < NW) sw[lane] = w;
+        }
+        const int status = __shfl((int)w, (int)W_STATUS, 64);
+        if (MODE == 0 && status == 0) {
+            // four chains per lane, each adding its words in the order it always has: of a lane's r words lane + 64 j the first r & ~3 go to
+            // chain j & 3, the last one to three to chain 0
+            double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+            for (uint32_t k = lane;;) {
+                const uint32_t r = k < nparts ? min(RW, (nparts - k + 63u) >> 6) : 0u, r4 = r & ~3u;
+#pragma unroll
+                for (uint32_t j = 0; j < RW; j += 4u) {
+                    if (j < r4) { s0 += v[j]; s1 += v[j + 1u]; s2 += v[j + 2u]; s3 += v[j + 3u]; }
+                    else { if (j < r) s0 += v[j]; if (j + 1u < r) s0 += v[j + 1u]; if (j + 2u < r) s0 += v[j + 2u]; }
+                }
+                k += 64u * RW;
+                if (k >= nparts) break;
+#pragma unroll
+                for (uint32_t j = 0; j < RW; ++j) v[j] = p[min(k + 64u * j, nparts - 1u)];
+            }
+            const double s = gr_wave_sum((s0 + s1) + (s2 + s3));
+            if (lane == 0) state[frame].rmsd = (float)sqrt(fmax(s, 0.0) / sum_w);
+        }
     }
-    if (lane < NW) reinterpret_cast<uint32_t *>(out_states + frame)[lane] = w;
-    __threadfence_system();
+    uint32_t add = 1u;
+    if (WPG > 1u) {
+        // the barrier's workgroup-scope release need not wait for a wave's stores on this target; the first wave's agent-scope release
+        // below is to cover them, so every wave sees its own acknowledged (s_waitcnt vmcnt(0)) before it arrives
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (wave != 0u) return;
+        add = min(WPG, nb - blockIdx.x * WPG);
+    }
     uint32_t n = 0u;
-    if (lane == 0) n = __hip_atomic_fetch_add(ctl_words + 12, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) + 1u;
+    if (lane == 0) n = __hip_atomic_fetch_add(ctl_words + 12, add, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) + add;
     n = (uint32_t)__builtin_amdgcn_readfirstlane((int)n);
     if (n != done_target) return;
+    // the last wave: nb x 88 bytes as 16-byte pieces (+ one 8-byte word when nb is odd)
+    const unsigned long long *src = reinterpret_cast<const unsigned long long *>(state);
+    const uint32_t n8 = nb * (uint32_t)(sizeof(GrFrameState) / 8u), n16 = n8 >> 1;
+    uint4 *dst = reinterpret_cast<uint4 *>(out_states);
+    for (uint32_t base = 0; base < n16; base += 64u * GR_RES_CLOSE_UNROLL) {
+        unsigned long long a[GR_RES_CLOSE_UNROLL], b[GR_RES_CLOSE_UNROLL];
+#pragma unroll
+        for (uint32_t u = 0; u < GR_RES_CLOSE_UNROLL; ++u) {      // (a piece past the end reads the last one again: every load is issued before the first store)
+            const uint32_t i = min(base + u * 64u + lane, n16 - 1u);
+            a[u] = gr_ld_agent(src + 2u * (size_t)i); b[u] = gr_ld_agent(src + 2u * (size_t)i + 1u);
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < GR_RES_CLOSE_UNROLL; ++u) {
+            const uint32_t i = base + u * 64u + lane;
+            if (i < n16) dst[i] = make_uint4((uint32_t)a[u], (uint32_t)(a[u] >> 32), (uint32_t)b[u], (uint32_t)(b[u] >> 32));
+        }
+    }
+    if ((n8 & 1u) && lane == 0) reinterpret_cast<unsigned long long *>(out_states)[n8 - 1u] = gr_ld_agent(src + n8 - 1u);
     if (lane < 12u) out_words[lane] = gr_ld_agent(ctl_words + lane);
     __threadfence_system();
     if (lane == 0) __hip_atomic_store(out_seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
