@@ -17,6 +17,9 @@
 // EVERY path of a small selection goes through these waves (centre stages of batches and of atoms_center, RMSD batches, the literal redo of
 // a frame whose image proof failed: k_center_small_stage / _pbc, k_rmsd_small<0 / 1> with one wave per frame), and a batch keeps
 // equalling its per-frame calls bit for bit.
+// The edges of the loops below -- one lane, one 4-atom group, a half and a full trip, two trips, the threshold, every start % 4, starts around
+// a tile boundary, a selection ending on the system's last atom, ragged gather lists, weights that are not the target's masses, NaN
+// neighbours in the straddling groups -- are pinned by tests/test_gpu_small_edges.py.
 #pragma once
 #include "gr_kernels.h"
 

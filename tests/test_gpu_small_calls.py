@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+from small_ref import BOXES, make, warm
 
 pytestmark = pytest.mark.gpu
 
@@ -21,44 +22,9 @@ def G():
 
 @pytest.fixture(scope="module", autouse=True)
 def warm_single_wave_kernels(G):
-    """Every single-wave kernel variant once, untimed, on a throwaway context: the FIRST launch of a kernel in a process (code-object load
-    on a cold box) can outlast the 20 ms the host polls for a small call's result -- the call then synchronises the stream instead and
-    counts it (GR_STAT_SMALL_SYNC_FALLBACKS).  With the kernels loaded, the tests below assert that counter stays 0 on their own
-    contexts: the polling path must be the one the tests exercise (round 4 had dropped the assertion instead)."""
-    box = O.box_from_lengths_angles([6.0, 6.0, 6.0], [60.0, 60.0, 90.0])
-    s, frames, m, rng = make(G, 2000, 2, box, 1)
-    s.group_create_from_ranges("a", [(10, 300)]); s.group_create_from_indices("b", np.unique(rng.integers(0, 2000, 200)))
-    ref = G.System(2000, masses=m, box=box, positions=frames[2])
-    ref.group_create_from_ranges("a", [(10, 300)]); ref.group_create_from_indices("b", np.unique(rng.integers(0, 2000, 200)))
-    for name in ("a", "b"):
-        for fn in ("group_get_com", "group_get_center", "group_estimate_com", "group_estimate_center", "group_get_com_naive", "group_get_center_naive"):
-            if hasattr(s, fn):
-                getattr(s, fn)(name, slot=0)
-        s.group_get_com_batch(name, 0, 2)
-    s.group_distance("a", "b", G.Dimension.XYZ, slot=0)
-    plan = G.RMSDPlan(ref, s, "a")
-    plan.rmsd(0, 1); plan.rmsd(0, 2); plan.rmsd_fit(0, 1); plan.rmsd_fit(0, 2)
-    plan.close(); ref.close(); s.close()
+    """every single-wave kernel loaded before the tests assert that no call fell back to a stream synchronisation (small_ref.warm)"""
+    warm(G)
     yield
-
-
-BOXES = {
-    "orthorhombic": ([6.44, 6.76, 7.26], [90.0, 90.0, 90.0]),
-    "dodecahedron": ([7.0, 7.0, 7.0], [60.0, 60.0, 90.0]),
-    "triclinic": ([7.5, 7.0, 6.5], [75.0, 80.0, 70.0]),
-}
-
-
-def make(G, n, nf, box, seed, spread=0.5):
-    rng = np.random.default_rng(seed)
-    masses = rng.uniform(1.0, 16.0, n).astype(np.float32)
-    s = G.System(n, masses=masses, n_slots=nf + 1)
-    frames = []
-    for f in range(nf + 1):
-        blob = rng.normal(0, spread, (n, 3)) + rng.uniform(0.1, 0.9, 3) * np.array([box[0], box[1], box[2]])
-        pos = O.wrap_atoms(blob.astype(np.float32), np.arange(n), box)
-        s.set_frame(pos, box, slot=f); frames.append(pos)
-    return s, frames, masses, rng
 
 
 @pytest.mark.parametrize("cell", list(BOXES))

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Randomised soak of the single-wave kernels of one-frame calls (gr_small.h, GR_TUNE_SMALL_CALLS) on the GPU box: systems of 300 .. 20 000
 atoms, selections of 1 .. 4 096 atoms drawn as one block or as scattered indices, three cells, blobs narrow enough for the image proof
-or wide enough to fail it, an atom without position or without mass inside the selection now and then.  Every call -- naive COM, Bai-Breen
+or wide enough to fail it, an atom without position or without mass inside the selection now and then, the reference's masses its own
+(drawn independently of the target's) in half of the cases.  Every call -- naive COM, Bai-Breen
 estimate (centre and COM), get_center / get_com, group_distance of two groups, calc_rmsd, calc_rmsd_and_fit (one frame per call and as a
 batch) -- is compared with the batched kernels (GR_TUNE_SMALL_CALLS = 0) on the same frames: the same error (variant and atom index) or
 centres to 5e-6 nm, rmsd to 2e-6, rotations to the conditioning of their Kabsch problem and fitted coordinates to 1.5e-5 + |dR| x distance from
@@ -91,7 +92,11 @@ while time.time() < t_end:
         s.set_tuning(small_calls=small)
         systems.append(s)
     S, B = systems
-    ref = G.System(n, masses=np.nan_to_num(masses, nan=1.0), box=box, positions=np.nan_to_num(frames[nf], nan=1.0))
+    # half of the cases: the reference carries masses of its own, so the plan's weights are not the target's masses (GrPlanDev::w_is_mass = 0:
+    # the second weight load and the separate sums of w v, in the single-wave kernels as in the batched ones)
+    own_w = rng.random() < 0.5
+    ref_masses = rng.uniform(1.0, 16.0, n).astype(np.float32) if own_w else np.nan_to_num(masses, nan=1.0)
+    ref = G.System(n, masses=ref_masses, box=box, positions=np.nan_to_num(frames[nf], nan=1.0))
     ref.group_create_from_indices("a", ia) if kind_a == "scattered" else ref.group_create_from_ranges("a", [(int(ia[0]), int(ia[-1]))])
     ok = True
     why = ""
@@ -163,8 +168,8 @@ while time.time() < t_end:
                     lim = 1.5e-5 + 1.05 * dR * lever
                     # conditioning of the rotation: H = sum (p - <p>)(q - <q>)^T over the group, reference against this frame's images
                     P = np.nan_to_num(ref.get_positions(0)[ia]).astype(np.float64); Q = np.nan_to_num(pb[ia] if pb.shape[0] == n else pb).astype(np.float64)
-                    wts = np.nan_to_num(masses[ia], nan=1.0).astype(np.float64)[:, None]
-                    Hc = (P - (wts * P).sum(0) / wts.sum()).T @ (Q - (wts * Q).sum(0) / wts.sum())      # (unweighted, about the centres of mass: rmsd.rs:567-570)
+                    wts = np.nan_to_num(masses[ia], nan=1.0).astype(np.float64)[:, None]; wts_ref = ref_masses[ia].astype(np.float64)[:, None]
+                    Hc = (P - (wts_ref * P).sum(0) / wts_ref.sum()).T @ (Q - (wts * Q).sum(0) / wts.sum())      # (unweighted, about the centres of mass: rmsd.rs:567-570)
                     sv = np.linalg.svd(Hc, compute_uv=False)
                     kappa = sv[0] / max(sv[1] + (1.0 if np.linalg.det(Hc) > 0 else -1.0) * sv[2], 1e-30)
                     if dR > 1e-6 * kappa + 3e-6:
@@ -178,7 +183,7 @@ while time.time() < t_end:
                     if os.environ.get("GR_FUZZ_DUMP") and not os.path.exists(os.environ["GR_FUZZ_DUMP"]):
                         np.savez(os.environ["GR_FUZZ_DUMP"], frames=np.stack(frames), masses=masses, ia=ia, box=box, f=f, scattered=(kind_a == "scattered"))
                     with O.acc64():
-                        ro, want = O.calc_rmsd_and_fit(np.nan_to_num(frames[nf], nan=1.0), np.nan_to_num(masses, nan=1.0), ia, box, frames[f], np.nan_to_num(masses, nan=1.0), ia, box)
+                        ro, want = O.calc_rmsd_and_fit(np.nan_to_num(frames[nf], nan=1.0), ref_masses, ia, box, frames[f], np.nan_to_num(masses, nan=1.0), ia, box)
                     print("note: n=%d group=%d frame %d: fitted coordinates %.3g apart at atom %d, %.2f nm from the group; |dR|_F %.3g, sigma1 / (sigma2 +- sigma3) %.3g; the group's own atoms %.3g apart; "
                           "against the oracle (fp64 sums): single wave %.3g, batched %.3g (group atoms %.3g / %.3g); rmsd %.7g: single wave %+.2g, batched %+.2g"
                           % (n, ia.size, f, d[k], k, lever[k], dR, kappa, float(d[ia].max()), float(np.nanmax(np.abs(pa - want))), float(np.nanmax(np.abs(pb - want))),
@@ -197,8 +202,8 @@ while time.time() < t_end:
     cases += 1
     bad += 0 if ok else 1
     if cases <= 30 or not ok:
-        print("%s n=%d a=%s(%d) b=%s(%d) cell=%s frames=%d %s%s%s" % ("ok " if ok else "BAD", n, kind_a, ia.size, kind_b, ib.size, "/".join("%g" % x for x in angles), nf,
-                                                                    "wide " if wide else "", "poisoned " if poison else "", why), flush=True)
+        print("%s n=%d a=%s(%d) b=%s(%d) cell=%s frames=%d %s%s%s%s" % ("ok " if ok else "BAD", n, kind_a, ia.size, kind_b, ib.size, "/".join("%g" % x for x in angles), nf,
+                                                                      "wide " if wide else "", "poisoned " if poison else "", "own-weights " if own_w else "", why), flush=True)
     for x in (S, B, ref): x.close()
 print("largest |dR|_F between the two paths %.3g, fitted coordinates at most %.3g nm apart" % (worst_dr, worst_xyz))
 print("%d cases, %d mismatches, %d calls answered by the single-wave kernels; %d ill-conditioned cases (a group spread over the whole cell) not compared" % (cases, bad, small_total, ill))
