@@ -44,6 +44,7 @@ typedef struct gr_segments gr_segments;
 typedef struct gr_region gr_region;
 typedef struct gr_contacts gr_contacts;
 typedef struct gr_rmsd_panel gr_rmsd_panel;
+typedef struct gr_fluct gr_fluct;
 typedef struct gr_xtc gr_xtc;
 
 /* status codes; 1..7 map onto the reference's error enums (src/errors.rs) */
@@ -840,6 +841,56 @@ int gr_rmsd_panel_status(const gr_rmsd_panel *p, int *out /* [frames] */);
 int gr_rmsd_panel_set_block_entries(gr_rmsd_panel *p, uint64_t n);  /* 0: default; the result never depends on it */
 int gr_rmsd_matrix(gr_rmsd_panel *rows, gr_rmsd_panel *cols /* or NULL */, float *out /* [n_rows][n_cols], host */);
 int gr_rmsd_matrix_device(gr_rmsd_panel *rows, gr_rmsd_panel *cols /* or NULL */, float **out_dev, uint32_t *n_rows, uint32_t *n_cols);
+
+/* ---------------------------------------------------------------- Fluctuations: mean structure and per-atom RMSF over resident frames
+ * The loop every analysis script writes around calc_rmsd_and_fit (the reference has no function for it): add up the fitted frames, take
+ * the average structure and the root mean square fluctuation of every atom.  Per atom and component the object keeps on the device an
+ * ORIGIN o (f32: the position in the first frame the object ever counted), s = sum d (f64) and q = sum d * d (f64) with d = x - o, one
+ * f32 subtraction that is then widened (d * d is exact in f64).  Frames are added in ascending order, one after another, by the lane that
+ * owns the atom: s and q depend on the SEQUENCE of counted frames alone -- not on how it was cut into calls, 1024-frame segments or grids
+ * -- and no atomic touches them.  Positions are taken as they are (no box is needed, nothing is unwrapped: the frames are expected to be
+ * fitted or whole).  The object keeps a pointer to its context: destroy it first.
+ *   gr_fluct_create            snapshots the group's atoms (S atoms, group order); the group may change or go afterwards.
+ *                              GR_E_GROUP_NOT_FOUND, GR_E_EMPTY_GROUP.
+ *   gr_fluct_accumulate_batch  counts the n_frames slots from first_slot.  A frame in which an atom of the snapshot has no position fails
+ *                              with GR_E_NO_POSITION and gr_last_error_index = the lowest such atom, and is counted for NO atom (a check
+ *                              kernel decides per frame before anything is added); when the first frame fails the origin comes from the
+ *                              first frame that is counted.  Batch rules: status_out[f] is each frame's status, the return value, message
+ *                              and index are the first failed frame's, a hard error writes nothing.  Frames and slots are never modified.
+ *   gr_fluct_clear             forgets every frame (and the origin)
+ *   gr_fluct_frames            counted frames;  gr_fluct_n_atoms: atoms of the snapshot
+ *   gr_fluct_read              closes the sums on the host, in f64, with n counted frames: mean[k][c] = o + s / n, var[k][c] =
+ *                              max(q - s^2 / n, 0) / n, rmsf[k] = sqrt(var_x + var_y + var_z); group order; each may be NULL.  n == 0:
+ *                              all three are NaN and the call returns GR_OK.
+ *   gr_fluct_read_raw          o, s, q as they stand ([S][3] each, group order) and n; each may be NULL
+ *   gr_fluct_merge             adds src's frames to dst (the shards of gr_pool_* / gr_comm_* runs, two contexts, two devices).  Different
+ *                              numbers of atoms: GR_E_INCONSISTENT_GROUP (counts = dst's, src's).  An empty src changes nothing; an empty
+ *                              dst takes src's origin and sums unchanged; else src's sums are moved to dst's origin in f64, delta = o_src
+ *                              - o_dst: s += s_src + n_src delta, q += q_src + 2 delta s_src + n_src delta^2.  Done on the host (60 B per
+ *                              atom).  AFTER A MERGE THE SUMS ARE NO LONGER THOSE OF A SEQUENTIAL WALK: they are as accurate, but bit for
+ *                              bit they depend on where the frames were split.  dst == src: GR_E_INVALID_ARG.
+ *   gr_fluct_store_mean        writes the mean, rounded to f32, into the snapshot's atoms of `slot` of dst -- any context on the same
+ *                              device with the same number of atoms, the object's own included (else GR_E_INVALID_ARG; n == 0 too).  Every
+ *                              other atom, the pads and the slot's box stay as they are: the slot is the reference of a new
+ *                              gr_rmsd_plan_create ("fit to the average, iterate").  Errors are reported on the object's context.
+ *   gr_fluct_set_launch        test hook: the ranges the group is cut into (one wave each; 0: one per 64 units -- 4-atom groups of the
+ *                              span, or list entries) and a cap on the grid of the position check.  The result never depends on it.
+ *   gr_fluct_stat              GR_FL_STAT_*: launches so far, the grids of the last one, the form the snapshot is walked in (0 a
+ *                              contiguous block, 1 an index list, 2 a span with a bit mask: at least half of the span's atoms are the
+ *                              group's), the frames a lane has in flight */
+enum { GR_FL_STAT_LAUNCHES = 1, GR_FL_STAT_LAST_RANGE_GROUPS = 2, GR_FL_STAT_LAST_CHECK_GROUPS = 3, GR_FL_STAT_FORM = 4, GR_FL_STAT_AHEAD = 5 };
+gr_fluct *gr_fluct_create(gr_ctx *ctx, const char *group, int *status);
+void gr_fluct_destroy(gr_fluct *f);
+int gr_fluct_accumulate_batch(gr_fluct *f, uint32_t first_slot, uint32_t n_frames, int *status_out /* [n_frames] or NULL */);
+int gr_fluct_clear(gr_fluct *f);
+uint64_t gr_fluct_frames(const gr_fluct *f);
+uint64_t gr_fluct_n_atoms(const gr_fluct *f);
+int gr_fluct_read(gr_fluct *f, double *mean /* [S][3] */, double *var /* [S][3] */, double *rmsf /* [S] */);
+int gr_fluct_read_raw(gr_fluct *f, float *origin /* [S][3] */, double *sum /* [S][3] */, double *sumsq /* [S][3] */, uint64_t *n);
+int gr_fluct_merge(gr_fluct *dst, gr_fluct *src);
+int gr_fluct_store_mean(gr_fluct *f, gr_ctx *dst, uint32_t slot);
+int gr_fluct_set_launch(gr_fluct *f, uint32_t range_groups, uint32_t check_groups);   /* 0: default; the result never depends on it */
+int gr_fluct_stat(const gr_fluct *f, int key, uint64_t *value);
 
 /* ---------------------------------------------------------------- xtc reader (host side)
  * The stage in front of the path: XtcReader (src/io/xtc_io/mod.rs, molly_xtc.rs:96-308, xdrfile_xtc.rs:42-104).

@@ -1032,4 +1032,66 @@ class RmsdPanel {
     gr_rmsd_panel *p_ = nullptr;
 };
 
+// ---- Fluctuations: the mean structure and the per-atom RMSF of a group over blocks of resident frames (the loop users write around
+// calc_rmsd_and_fit: the reference has no function for it).  The sums are added frame after frame, so they do not depend on how the
+// frames were cut into calls; after merge() they are no longer those of one sequential walk.
+class Fluctuations {
+  public:
+    struct Raw { std::vector<float> origin; std::vector<double> sum, sumsq; uint64_t n = 0; };    // [S][3] each, group order
+
+    Fluctuations(System &system, const std::string &group) : ctx_(system.raw()) {
+        int st = 0;
+        f_ = gr_fluct_create(ctx_, group.c_str(), &st);
+        if (!f_) raise(st);
+    }
+    ~Fluctuations() { if (f_) gr_fluct_destroy(f_); }
+    Fluctuations(const Fluctuations &) = delete;
+    Fluctuations &operator=(const Fluctuations &) = delete;
+    Fluctuations(Fluctuations &&o) noexcept : ctx_(o.ctx_), f_(o.f_) { o.f_ = nullptr; }
+
+    uint64_t frames() const { return gr_fluct_frames(f_); }
+    uint64_t n_atoms() const { return gr_fluct_n_atoms(f_); }
+    // counts n_frames slots from first_slot; a failed frame (an atom of the group without position) is counted for no atom and throws
+    // the first failure unless `status` is given
+    void accumulate(uint32_t first_slot, uint32_t n_frames, std::vector<int> *status = nullptr) {
+        std::vector<int> st(n_frames);
+        const int r = gr_fluct_accumulate_batch(f_, first_slot, n_frames, st.data());
+        if (status && r != GR_E_INVALID_ARG && r != GR_E_HIP) *status = st;
+        else if (r != GR_OK) raise(r);
+    }
+    void clear() { check(gr_fluct_clear(f_)); }
+    // mean [S][3], variance per axis [S][3], rmsf [S]: NaN before the first counted frame
+    std::vector<double> mean() { std::vector<double> m(3 * n_atoms() + 1); check(gr_fluct_read(f_, m.data(), nullptr, nullptr)); m.resize(3 * n_atoms()); return m; }
+    std::vector<double> variance() { std::vector<double> v(3 * n_atoms() + 1); check(gr_fluct_read(f_, nullptr, v.data(), nullptr)); v.resize(3 * n_atoms()); return v; }
+    std::vector<double> rmsf() { std::vector<double> r(n_atoms() + 1); check(gr_fluct_read(f_, nullptr, nullptr, r.data())); r.resize(n_atoms()); return r; }
+    Raw raw() {
+        Raw r;
+        const size_t n = 3 * n_atoms();
+        r.origin.resize(n + 1); r.sum.resize(n + 1); r.sumsq.resize(n + 1);
+        check(gr_fluct_read_raw(f_, r.origin.data(), r.sum.data(), r.sumsq.data(), &r.n));
+        r.origin.resize(n); r.sum.resize(n); r.sumsq.resize(n);
+        return r;
+    }
+    void merge(Fluctuations &src) { check(gr_fluct_merge(f_, src.f_)); }
+    // the mean, rounded to f32, into the group's atoms of `slot` of `dst` (same device, same number of atoms): the reference of a new RmsdPlan
+    void store_mean(System &dst, uint32_t slot) { check(gr_fluct_store_mean(f_, dst.raw(), slot)); }
+    void set_launch(uint32_t range_groups, uint32_t check_groups) { gr_fluct_set_launch(f_, range_groups, check_groups); }
+    uint64_t stat(int key) const { uint64_t v = 0; if (gr_fluct_stat(f_, key, &v) != GR_OK) throw std::invalid_argument("Fluctuations::stat | unknown key"); return v; }
+    gr_fluct *raw_handle() const { return f_; }
+
+  private:
+    void check(int st) const { if (st != GR_OK) raise(st); }
+    [[noreturn]] void raise(int st) const {
+        switch (st) {
+        case GR_E_GROUP_NOT_FOUND: throw Error("GroupError", "NotFound", st);
+        case GR_E_EMPTY_GROUP: throw Error("GroupError", "EmptyGroup", st);
+        case GR_E_INCONSISTENT_GROUP: throw Error("GroupError", "InconsistentGroup", st);
+        case GR_E_NO_POSITION: throw Error("GroupError", "InvalidPosition", st, gr_last_error_index(ctx_));
+        default: throw Error("DeviceError", std::string(gr_status_string(st)) + ": " + gr_last_error(ctx_), st);
+        }
+    }
+    gr_ctx *ctx_ = nullptr;
+    gr_fluct *f_ = nullptr;
+};
+
 }  // namespace groan

@@ -73,6 +73,7 @@ pub const GR_CT_STAT_LAST_WALK_GROUPS: c_int = 9;
 #[repr(C)] pub struct gr_region { _private: [u8; 0] }
 #[repr(C)] pub struct gr_contacts { _private: [u8; 0] }
 #[repr(C)] pub struct gr_rmsd_panel { _private: [u8; 0] }
+#[repr(C)] pub struct gr_fluct { _private: [u8; 0] }
 #[repr(C)] pub struct gr_pool { _private: [u8; 0] }
 #[repr(C)] pub struct gr_comm { _private: [u8; 0] }
 /// `body(ctx, worker, frame, user, result)` of gr_pool_map: non-zero return = the frame's error (the first one wins)
@@ -231,6 +232,19 @@ extern "C" {
     pub fn gr_rmsd_panel_set_block_entries(p: *mut gr_rmsd_panel, n: u64) -> c_int;
     pub fn gr_rmsd_matrix(rows: *mut gr_rmsd_panel, cols: *mut gr_rmsd_panel, out: *mut c_float) -> c_int;
     pub fn gr_rmsd_matrix_device(rows: *mut gr_rmsd_panel, cols: *mut gr_rmsd_panel, out_dev: *mut *mut c_float, n_rows: *mut u32, n_cols: *mut u32) -> c_int;
+    // Fluctuations: mean structure and per-atom RMSF of a group accumulated over resident frames (status_out and the outputs of read / read_raw may be null)
+    pub fn gr_fluct_create(ctx: *mut gr_ctx, group: *const c_char, status: *mut c_int) -> *mut gr_fluct;
+    pub fn gr_fluct_destroy(f: *mut gr_fluct);
+    pub fn gr_fluct_accumulate_batch(f: *mut gr_fluct, first_slot: u32, n_frames: u32, status_out: *mut c_int) -> c_int;
+    pub fn gr_fluct_clear(f: *mut gr_fluct) -> c_int;
+    pub fn gr_fluct_frames(f: *const gr_fluct) -> u64;
+    pub fn gr_fluct_n_atoms(f: *const gr_fluct) -> u64;
+    pub fn gr_fluct_read(f: *mut gr_fluct, mean: *mut f64, var: *mut f64, rmsf: *mut f64) -> c_int;
+    pub fn gr_fluct_read_raw(f: *mut gr_fluct, origin: *mut c_float, sum: *mut f64, sumsq: *mut f64, n: *mut u64) -> c_int;
+    pub fn gr_fluct_merge(dst: *mut gr_fluct, src: *mut gr_fluct) -> c_int;
+    pub fn gr_fluct_store_mean(f: *mut gr_fluct, dst: *mut gr_ctx, slot: u32) -> c_int;
+    pub fn gr_fluct_set_launch(f: *mut gr_fluct, range_groups: u32, check_groups: u32) -> c_int;
+    pub fn gr_fluct_stat(f: *const gr_fluct, key: c_int, value: *mut u64) -> c_int;
     pub fn gr_ctx_set_tuning(ctx: *mut gr_ctx, key: c_int, value: i64) -> c_int;   // GR_TUNE_* (include/groan_hip.h)
     pub fn gr_host_alloc(bytes: usize) -> *mut c_void;                              // pinned memory: asynchronous gr_frame_upload
     pub fn gr_host_free(p: *mut c_void);
