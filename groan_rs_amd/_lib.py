@@ -30,6 +30,9 @@ RG_STAT_LAST_LAUNCHES, RG_STAT_LAST_PIECES, RG_STAT_LAST_TOTAL, RG_STAT_CHUNK = 
 CT_STAT_LAST_LAUNCHES, CT_STAT_LAST_PIECES, CT_STAT_LAST_TOTAL, CT_STAT_TILE = 1, 2, 3, 4
 CT_STAT_LAST_RUNS, CT_STAT_LAST_CELLS, CT_STAT_LAST_RUN_CELLS_MIN, CT_STAT_LAST_RUN_CELLS_MAX, CT_STAT_LAST_WALK_GROUPS = 5, 6, 7, 8, 9
 FL_STAT_LAUNCHES, FL_STAT_LAST_RANGE_GROUPS, FL_STAT_LAST_CHECK_GROUPS, FL_STAT_FORM, FL_STAT_AHEAD = 1, 2, 3, 4, 5
+CV_STAT_LAUNCHES, CV_STAT_LAST_PRODUCT_GROUPS, CV_STAT_LAST_CHECK_GROUPS, CV_STAT_BLOCK_EDGE, CV_STAT_TRIP_FRAMES, CV_STAT_BLOCKS = 1, 2, 3, 4, 5, 6
+CV_MASS_WEIGHTED = 1
+CV_MAX_ATOMS = 4096
 CT_MAX_BINS = 4096
 MAX_SHAPES = 8
 
@@ -208,6 +211,18 @@ SIGNATURES = {
     "gr_fluct_store_mean": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "gr_fluct_set_launch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
     "gr_fluct_stat": (C.c_int, [C.c_void_p, C.c_int, c_u64p]),
+    "gr_covar_create": (C.c_void_p, [C.c_void_p, C.c_char_p, c_i32p]),
+    "gr_covar_destroy": (None, [C.c_void_p]),
+    "gr_covar_accumulate_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "gr_covar_clear": (C.c_int, [C.c_void_p]),
+    "gr_covar_frames": (C.c_uint64, [C.c_void_p]),
+    "gr_covar_n_atoms": (C.c_uint64, [C.c_void_p]),
+    "gr_covar_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
+    "gr_covar_read_raw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_u64p]),
+    "gr_covar_read_dccm": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gr_covar_merge": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gr_covar_set_launch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
+    "gr_covar_stat": (C.c_int, [C.c_void_p, C.c_int, c_u64p]),
     "gr_group_center_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "gr_group_translate_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_void_p, C.c_void_p]),
     "gr_group_wrap_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_void_p]),

@@ -3735,3 +3735,4 @@ int gr_synth_uniform(gr_ctx *c, uint32_t slot, const float *box9, uint64_t seed)
 #include "gr_contacts.h" // Contacts: cut-off pair search over a block of resident frames: kernels, object and C ABI
 #include "gr_rmsd_panel.h" // RMSDPanel: packed centred frames and their all-pairs RMSD matrix (f64 MFMA product): kernels, object and C ABI
 #include "gr_fluct.h"    // Fluctuations: mean structure and per-atom RMSF accumulated over batches of resident frames: kernels, object and C ABI
+#include "gr_covar.h"    // Covariance: positional covariance matrix and DCCM accumulated over batches of resident frames (f64 MFMA rank-K update): kernels, object and C ABI

@@ -45,6 +45,7 @@ typedef struct gr_region gr_region;
 typedef struct gr_contacts gr_contacts;
 typedef struct gr_rmsd_panel gr_rmsd_panel;
 typedef struct gr_fluct gr_fluct;
+typedef struct gr_covar gr_covar;
 typedef struct gr_xtc gr_xtc;
 
 /* status codes; 1..7 map onto the reference's error enums (src/errors.rs) */
@@ -891,6 +892,61 @@ int gr_fluct_merge(gr_fluct *dst, gr_fluct *src);
 int gr_fluct_store_mean(gr_fluct *f, gr_ctx *dst, uint32_t slot);
 int gr_fluct_set_launch(gr_fluct *f, uint32_t range_groups, uint32_t check_groups);   /* 0: default; the result never depends on it */
 int gr_fluct_stat(const gr_fluct *f, int key, uint64_t *value);
+
+/* ---------------------------------------------------------------- Covariance: positional covariance and DCCM over resident frames
+ * The step after Fluctuations (the reference has no function for it): the full second moment of the fitted coordinates -- the 3S x 3S
+ * covariance matrix of essential dynamics / PCA (gmx covar), optionally mass-weighted, and the S x S dynamical cross-correlation map.
+ * For a snapshot of a group's S atoms (group order; D = 3S, dimension 3k + c) the object keeps on the device the ORIGIN o (f32 [D]: the
+ * position in the first frame the object ever counted), s = sum d (f64 [D]) and Q = sum d_i d_j (f64 [D][D], the upper block triangle
+ * stored) with d = x - o, one f32 subtraction that is then widened (every product is exact in f64).  Q grows by a symmetric rank-K update
+ * on the f64 matrix cores: every entry belongs to one wave, which takes the stored value as its accumulator and adds the frames of a
+ * segment in ascending trips of GR_CV_STAT_TRIP_FRAMES as one chain -- no split of the frames over waves, no partial sums, no atomics.
+ * The bits of the state are therefore a function of the SEQUENCE OF CALLS alone (their frames and where the calls cut them): not of the
+ * grid, gr_covar_set_launch, the context's history or the run; failed frames enter as zeros, which are neutral bit for bit.  Q is exactly
+ * symmetric.  NOT guaranteed: the same bits when the same frames are cut into calls differently -- one matrix instruction adds four
+ * frames in an order the hardware does not document, so different cuts agree to the rounding bound 2 n 2^-53 sum |d_i d_j| only.
+ * Positions are taken as they are (frames are expected to be fitted).  The eigen-solve is the caller's (LAPACK dsyevd / numpy.linalg.eigh
+ * on gr_covar_read).  The object keeps a pointer to its context: destroy it first.
+ *   gr_covar_create            snapshots the group's atoms and their masses.  GR_E_GROUP_NOT_FOUND, GR_E_EMPTY_GROUP; more than
+ *                              GR_CV_MAX_ATOMS atoms: GR_E_INVALID_ARG (the message names the cap; Q takes 36 S^2 bytes on the device).
+ *   gr_covar_accumulate_batch  counts the n_frames slots from first_slot; Fluctuations' contract: a frame in which an atom of the snapshot
+ *                              has no position fails with GR_E_NO_POSITION and gr_last_error_index = the lowest such atom and is counted
+ *                              for NO dimension; when the first frame fails the origin comes from the first frame that is counted; a frame
+ *                              without a box is counted.  Batch rules: status_out[f] is each frame's status, the return value, message
+ *                              and index are the first failed frame's, a hard error writes nothing.  Frames and slots are never modified.
+ *   gr_covar_clear             forgets every frame (and the origin)
+ *   gr_covar_frames            counted frames;  gr_covar_n_atoms: atoms of the snapshot
+ *   gr_covar_read_raw          o [D], s [D], Q [D][D] (the full square, mirrored on the host) as they stand, and n; each may be NULL
+ *   gr_covar_read              closes the sums on the host, in f64, with n counted frames: mean[i] = o + s / n, cov[i][j] = (Q_ij - s_i
+ *                              s_j / n) / n (divided by n, as gr_fluct_read); flags & GR_CV_MASS_WEIGHTED: times sqrt(m_i) sqrt(m_j), the
+ *                              masses of the snapshot (NaN where a mass was never set).  Each may be NULL.  n == 0: NaN, GR_OK.
+ *   gr_covar_read_dccm         corr[a][b] = sum_c cov[3a+c][3b+c] / sqrt(tr_a tr_b), tr_a = sum_c cov[3a+c][3a+c], unweighted, f64 [S][S].
+ *                              An atom with tr = 0 has 1.0 on the diagonal and NaN elsewhere in its row and column.  n == 0: NaN.
+ *   gr_covar_merge             adds src's frames to dst (same S; any context, any device), on the host in f64 with delta = o_src - o_dst:
+ *                              s += s_src + n_src delta, Q_ij += Q_src,ij + delta_i s_src,j + s_src,i delta_j + n_src delta_i delta_j.
+ *                              An empty src changes nothing, an empty dst takes src's state unchanged.  Different S:
+ *                              GR_E_INCONSISTENT_GROUP (counts = dst's, src's); dst == src: GR_E_INVALID_ARG.  AFTER A MERGE THE SUMS ARE
+ *                              NO LONGER THOSE OF ONE WALK: they are as accurate, but bit for bit they depend on where the frames were split.
+ *   gr_covar_set_launch        test hook: caps on the grid of the product (it then strides over the blocks) and of the position check
+ *                              (0: one workgroup per stored block / per 256 units).  The result never depends on it.
+ *   gr_covar_stat              GR_CV_STAT_*: launches so far, the grids of the last one, the edge of a block of Q in dimensions, the
+ *                              frames per trip of the product, the blocks of Q that are stored and computed */
+#define GR_CV_MAX_ATOMS 4096u      /* S at most: 613 MB of Q on the device, 1.2 GB for the square gr_covar_read returns */
+#define GR_CV_MASS_WEIGHTED 1u
+enum { GR_CV_STAT_LAUNCHES = 1, GR_CV_STAT_LAST_PRODUCT_GROUPS = 2, GR_CV_STAT_LAST_CHECK_GROUPS = 3, GR_CV_STAT_BLOCK_EDGE = 4, GR_CV_STAT_TRIP_FRAMES = 5,
+       GR_CV_STAT_BLOCKS = 6 };
+gr_covar *gr_covar_create(gr_ctx *ctx, const char *group, int *status);
+void gr_covar_destroy(gr_covar *cv);
+int gr_covar_accumulate_batch(gr_covar *cv, uint32_t first_slot, uint32_t n_frames, int *status_out /* [n_frames] or NULL */);
+int gr_covar_clear(gr_covar *cv);
+uint64_t gr_covar_frames(const gr_covar *cv);
+uint64_t gr_covar_n_atoms(const gr_covar *cv);
+int gr_covar_read(gr_covar *cv, double *mean /* [D] */, double *cov /* [D][D] */, uint32_t flags);
+int gr_covar_read_raw(gr_covar *cv, float *origin /* [D] */, double *sum /* [D] */, double *Q /* [D][D] */, uint64_t *n);
+int gr_covar_read_dccm(gr_covar *cv, double *corr /* [S][S] */);
+int gr_covar_merge(gr_covar *dst, gr_covar *src);
+int gr_covar_set_launch(gr_covar *cv, uint32_t product_groups, uint32_t check_groups);   /* 0: default; the result never depends on it */
+int gr_covar_stat(const gr_covar *cv, int key, uint64_t *value);
 
 /* ---------------------------------------------------------------- xtc reader (host side)
  * The stage in front of the path: XtcReader (src/io/xtc_io/mod.rs, molly_xtc.rs:96-308, xdrfile_xtc.rs:42-104).

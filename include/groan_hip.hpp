@@ -1094,4 +1094,69 @@ class Fluctuations {
     gr_fluct *f_ = nullptr;
 };
 
+// ---- Covariance: the positional covariance matrix (3S x 3S, optionally mass-weighted) and the dynamical cross-correlation map (S x S)
+// of a group over blocks of resident frames: the step after Fluctuations (essential dynamics; the reference has no function for it).
+// The state's bits depend on the sequence of calls alone; after merge() the sums are no longer those of one walk.  The eigen-solve is
+// the caller's (LAPACK dsyevd on matrix()).
+class Covariance {
+  public:
+    struct Raw { std::vector<float> origin; std::vector<double> sum, Q; uint64_t n = 0; };    // [D], [D], [D][D] (D = 3S, group order)
+
+    Covariance(System &system, const std::string &group) : ctx_(system.raw()) {
+        int st = 0;
+        f_ = gr_covar_create(ctx_, group.c_str(), &st);
+        if (!f_) raise(st);
+    }
+    ~Covariance() { if (f_) gr_covar_destroy(f_); }
+    Covariance(const Covariance &) = delete;
+    Covariance &operator=(const Covariance &) = delete;
+    Covariance(Covariance &&o) noexcept : ctx_(o.ctx_), f_(o.f_) { o.f_ = nullptr; }
+
+    uint64_t frames() const { return gr_covar_frames(f_); }
+    uint64_t n_atoms() const { return gr_covar_n_atoms(f_); }
+    // counts n_frames slots from first_slot; a failed frame (an atom of the group without position) is counted for no dimension and
+    // throws the first failure unless `status` is given
+    void accumulate(uint32_t first_slot, uint32_t n_frames, std::vector<int> *status = nullptr) {
+        std::vector<int> st(n_frames);
+        const int r = gr_covar_accumulate_batch(f_, first_slot, n_frames, st.data());
+        if (status && r != GR_E_INVALID_ARG && r != GR_E_HIP) *status = st;
+        else if (r != GR_OK) raise(r);
+    }
+    void clear() { check(gr_covar_clear(f_)); }
+    // mean [D], covariance [D][D] (divided by n; mass_weighted: times sqrt(m_i m_j)), DCCM [S][S]: NaN before the first counted frame
+    std::vector<double> mean() { std::vector<double> m(3 * n_atoms()); check(gr_covar_read(f_, m.data(), nullptr, 0)); return m; }
+    std::vector<double> matrix(bool mass_weighted = false) {
+        const size_t d = 3 * n_atoms();
+        std::vector<double> c(d * d);
+        check(gr_covar_read(f_, nullptr, c.data(), mass_weighted ? GR_CV_MASS_WEIGHTED : 0u));
+        return c;
+    }
+    std::vector<double> dccm() { std::vector<double> c(n_atoms() * n_atoms()); check(gr_covar_read_dccm(f_, c.data())); return c; }
+    Raw raw() {
+        Raw r;
+        const size_t d = 3 * n_atoms();
+        r.origin.resize(d); r.sum.resize(d); r.Q.resize(d * d);
+        check(gr_covar_read_raw(f_, r.origin.data(), r.sum.data(), r.Q.data(), &r.n));
+        return r;
+    }
+    void merge(Covariance &src) { check(gr_covar_merge(f_, src.f_)); }
+    void set_launch(uint32_t product_groups, uint32_t check_groups) { gr_covar_set_launch(f_, product_groups, check_groups); }
+    uint64_t stat(int key) const { uint64_t v = 0; if (gr_covar_stat(f_, key, &v) != GR_OK) throw std::invalid_argument("Covariance::stat | unknown key"); return v; }
+    gr_covar *raw_handle() const { return f_; }
+
+  private:
+    void check(int st) const { if (st != GR_OK) raise(st); }
+    [[noreturn]] void raise(int st) const {
+        switch (st) {
+        case GR_E_GROUP_NOT_FOUND: throw Error("GroupError", "NotFound", st);
+        case GR_E_EMPTY_GROUP: throw Error("GroupError", "EmptyGroup", st);
+        case GR_E_INCONSISTENT_GROUP: throw Error("GroupError", "InconsistentGroup", st);
+        case GR_E_NO_POSITION: throw Error("GroupError", "InvalidPosition", st, gr_last_error_index(ctx_));
+        default: throw Error("DeviceError", std::string(gr_status_string(st)) + ": " + gr_last_error(ctx_), st);
+        }
+    }
+    gr_ctx *ctx_ = nullptr;
+    gr_covar *f_ = nullptr;
+};
+
 }  // namespace groan

@@ -74,6 +74,7 @@ pub const GR_CT_STAT_LAST_WALK_GROUPS: c_int = 9;
 #[repr(C)] pub struct gr_contacts { _private: [u8; 0] }
 #[repr(C)] pub struct gr_rmsd_panel { _private: [u8; 0] }
 #[repr(C)] pub struct gr_fluct { _private: [u8; 0] }
+#[repr(C)] pub struct gr_covar { _private: [u8; 0] }
 #[repr(C)] pub struct gr_pool { _private: [u8; 0] }
 #[repr(C)] pub struct gr_comm { _private: [u8; 0] }
 /// `body(ctx, worker, frame, user, result)` of gr_pool_map: non-zero return = the frame's error (the first one wins)
@@ -245,6 +246,19 @@ extern "C" {
     pub fn gr_fluct_store_mean(f: *mut gr_fluct, dst: *mut gr_ctx, slot: u32) -> c_int;
     pub fn gr_fluct_set_launch(f: *mut gr_fluct, range_groups: u32, check_groups: u32) -> c_int;
     pub fn gr_fluct_stat(f: *const gr_fluct, key: c_int, value: *mut u64) -> c_int;
+    // Covariance: positional covariance matrix and DCCM of a group accumulated over resident frames (status_out and the outputs of read / read_raw may be null)
+    pub fn gr_covar_create(ctx: *mut gr_ctx, group: *const c_char, status: *mut c_int) -> *mut gr_covar;
+    pub fn gr_covar_destroy(cv: *mut gr_covar);
+    pub fn gr_covar_accumulate_batch(cv: *mut gr_covar, first_slot: u32, n_frames: u32, status_out: *mut c_int) -> c_int;
+    pub fn gr_covar_clear(cv: *mut gr_covar) -> c_int;
+    pub fn gr_covar_frames(cv: *const gr_covar) -> u64;
+    pub fn gr_covar_n_atoms(cv: *const gr_covar) -> u64;
+    pub fn gr_covar_read(cv: *mut gr_covar, mean: *mut f64, cov: *mut f64, flags: u32) -> c_int;
+    pub fn gr_covar_read_raw(cv: *mut gr_covar, origin: *mut c_float, sum: *mut f64, q: *mut f64, n: *mut u64) -> c_int;
+    pub fn gr_covar_read_dccm(cv: *mut gr_covar, corr: *mut f64) -> c_int;
+    pub fn gr_covar_merge(dst: *mut gr_covar, src: *mut gr_covar) -> c_int;
+    pub fn gr_covar_set_launch(cv: *mut gr_covar, product_groups: u32, check_groups: u32) -> c_int;
+    pub fn gr_covar_stat(cv: *const gr_covar, key: c_int, value: *mut u64) -> c_int;
     pub fn gr_ctx_set_tuning(ctx: *mut gr_ctx, key: c_int, value: i64) -> c_int;   // GR_TUNE_* (include/groan_hip.h)
     pub fn gr_host_alloc(bytes: usize) -> *mut c_void;                              // pinned memory: asynchronous gr_frame_upload
     pub fn gr_host_free(p: *mut c_void);
