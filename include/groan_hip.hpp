@@ -581,6 +581,20 @@ Data traj_iter_map_reduce(const std::vector<int> &devices, uint64_t n_frames,
     return Data::reduce(std::move(data));
 }
 
+// ---- the `status` argument of every batch method below (HBondPlan::batch .. Covariance::accumulate), one rule for all of them:
+// a frame that fails is reported in `status` when it is given (one entry per frame) and thrown -- the first failure -- when it is not.
+// A call that was REFUSED AS A WHOLE always throws, `status` given or not: it returned an error while every entry of the status
+// vector it filled is GR_OK, so no frame ran (a slot range outside the system, an unknown or empty group, a refused argument,
+// a HIP error).  `status` is not touched by a call that throws.
+namespace detail {
+template <typename Raise>
+inline void batch_status(int r, const std::vector<int> &st, std::vector<int> *status, Raise &&raise) {
+    if (r != GR_OK && std::all_of(st.begin(), st.end(), [](int s) { return s == GR_OK; })) raise(r);
+    if (status) *status = st;
+    else if (r != GR_OK) raise(r);
+}
+}  // namespace detail
+
 // ---- hydrogen bonds over a batch of resident frames (src/system/hbonds.rs): HBondAnalysis as a plan built once
 struct HBondChain { std::string acceptors, donors, hydrogens; };   // group names of the System (HBondChain::new)
 struct HBond { uint32_t donor, hydrogen, acceptor; float distance, angle; };
@@ -619,8 +633,7 @@ class HBondPlan {
             if (total <= cap_) break;
             cap_ = total + total / 4;                                    // capacity hint: one call per batch in steady state
         }
-        if (status) *status = st;
-        else if (r != GR_OK) raise(r, false);
+        detail::batch_status(r, st, status, [this](int e) { raise(e, false); });
         std::vector<std::vector<std::vector<HBond>>> out(n_frames, std::vector<std::vector<HBond>>(np));
         for (uint32_t f = 0; f < n_frames; ++f)
             for (size_t p = 0; p < np; ++p)
@@ -703,8 +716,7 @@ class GridMap {
         std::vector<int> st(n_frames);
         const int r = gr_gridmap_accumulate_batch(map_, first_slot, n_frames, group.c_str(), (int)value, offset ? offset->data() : nullptr, wrap ? GR_GM_WRAP : 0,
                                                   outside.data(), st.data());
-        if (status) *status = st;
-        else if (r != GR_OK) raise(r);
+        detail::batch_status(r, st, status, [this](int e) { raise(e); });
         return outside;
     }
     void clear() { const int st = gr_gridmap_clear(map_); if (st != GR_OK) raise(st); }
@@ -798,8 +810,7 @@ class Segments {
         std::vector<float> out((size_t)n_frames * size() * 3);
         std::vector<int> st(n_frames);
         const int r = gr_segments_center_batch(seg_, first_slot, n_frames, (int)kind, weighted ? 1 : 0, out.data(), st.data());
-        if (status) *status = st;
-        else if (r != GR_OK) raise(r);
+        detail::batch_status(r, st, status, [this](int e) { raise(e); });
         return out;
     }
     std::vector<float> get_com(uint32_t first_slot, uint32_t n_frames, std::vector<int> *status = nullptr) { return centers(first_slot, n_frames, CenterKind::Pbc, true, status); }
@@ -850,8 +861,7 @@ class Region {
         std::vector<int> st(n_frames);
         const int r = gr_region_select_batch(rg_, first_slot, n_frames, group.empty() ? nullptr : group.c_str(), anchors.empty() ? nullptr : anchors.data(),
                                              counts.data(), st.data());
-        if (status) *status = st;
-        else if (r != GR_OK) raise(r);
+        detail::batch_status(r, st, status, [this](int e) { raise(e); });
         return counts;
     }
     // the last selection: offsets[n_frames + 1] and the atom indices, frame after frame
@@ -916,8 +926,7 @@ class Contacts {
         std::vector<uint64_t> counts(n_frames);
         std::vector<int> st(n_frames);
         const int r = gr_contacts_pairs_batch(ct_, first_slot, n_frames, max_pairs, counts.data(), nullptr, st.data());
-        if (status) *status = st;
-        else if (r != GR_OK) raise(r);
+        detail::batch_status(r, st, status, [this](int e) { raise(e); });
         return counts;
     }
     // the last pairs call: offsets[n_frames + 1] and (i, j, d), frame after frame
@@ -937,9 +946,8 @@ class Contacts {
         std::vector<uint64_t> np(n_frames);
         std::vector<int> st(n_frames);
         const int r = gr_contacts_count_batch(ct_, first_slot, n_frames, per_atom.data(), np.data(), st.data());
+        detail::batch_status(r, st, status, [this](int e) { raise(e); });
         if (n_pairs) *n_pairs = np;
-        if (status) *status = st;
-        else if (r != GR_OK) raise(r);
         per_atom.resize((size_t)n_frames * n1_);
         return per_atom;
     }
@@ -948,8 +956,7 @@ class Contacts {
         std::vector<uint64_t> h((size_t)n_frames * nbins + 1);
         std::vector<int> st(n_frames);
         const int r = gr_contacts_hist_batch(ct_, first_slot, n_frames, nbins, h.data(), st.data());
-        if (status && r != GR_E_INVALID_ARG) *status = st;
-        else if (r != GR_OK) raise(r);
+        detail::batch_status(r, st, status, [this](int e) { raise(e); });
         h.resize((size_t)n_frames * nbins);
         return h;
     }
@@ -992,8 +999,7 @@ class RmsdPanel {
     void append(uint32_t first_slot, uint32_t n_frames, std::vector<int> *status = nullptr) {
         std::vector<int> st(n_frames);
         const int r = gr_rmsd_panel_append_batch(p_, first_slot, n_frames, st.data());
-        if (status && r != GR_E_INVALID_ARG && r != GR_E_HIP) *status = st;
-        else if (r != GR_OK) raise(r);
+        detail::batch_status(r, st, status, [this](int e) { raise(e); });
     }
     void clear() { gr_rmsd_panel_clear(p_); }
     std::vector<int> status() const { std::vector<int> s(frames() + 1); gr_rmsd_panel_status(p_, s.data()); s.resize(frames()); return s; }
@@ -1056,8 +1062,7 @@ class Fluctuations {
     void accumulate(uint32_t first_slot, uint32_t n_frames, std::vector<int> *status = nullptr) {
         std::vector<int> st(n_frames);
         const int r = gr_fluct_accumulate_batch(f_, first_slot, n_frames, st.data());
-        if (status && r != GR_E_INVALID_ARG && r != GR_E_HIP) *status = st;
-        else if (r != GR_OK) raise(r);
+        detail::batch_status(r, st, status, [this](int e) { raise(e); });
     }
     void clear() { check(gr_fluct_clear(f_)); }
     // mean [S][3], variance per axis [S][3], rmsf [S]: NaN before the first counted frame
@@ -1119,8 +1124,7 @@ class Covariance {
     void accumulate(uint32_t first_slot, uint32_t n_frames, std::vector<int> *status = nullptr) {
         std::vector<int> st(n_frames);
         const int r = gr_covar_accumulate_batch(f_, first_slot, n_frames, st.data());
-        if (status && r != GR_E_INVALID_ARG && r != GR_E_HIP) *status = st;
-        else if (r != GR_OK) raise(r);
+        detail::batch_status(r, st, status, [this](int e) { raise(e); });
     }
     void clear() { check(gr_covar_clear(f_)); }
     // mean [D], covariance [D][D] (divided by n; mass_weighted: times sqrt(m_i m_j)), DCCM [S][S]: NaN before the first counted frame

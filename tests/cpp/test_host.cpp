@@ -1,5 +1,7 @@
 // tests/cpp/test_host.cpp -- the C++ host mirror (include/groan_hip.hpp) exercised the way the reference's own
-// unit tests exercise the Rust API.  Built by __graft_entry__.build() (g++, links libgroan_hip.so), run on the
+// unit tests exercise the Rust API: System, AtomContainer, Shape, the iterators, the RMSD analyzer, the readers and
+// writers.  (The batch objects of the header's second half -- HBondPlan, GridMap, Segments, Region, Contacts, RmsdPanel,
+// Fluctuations, Covariance -- are test_objects.cpp's.)  Built by __graft_entry__.build() (g++, links libgroan_hip.so), run on the
 // GPU box by tests/test_gpu_cpp_host.py which passes a directory of raw little-endian fixtures:
 //   gro_keep.f32 [261][3]  frames.f32 [11][261][3]  boxes.f32 [11][9]  box0.f32 [9]  masses.f32 [261]
 #include <cmath>
