@@ -33,6 +33,10 @@ FL_STAT_LAUNCHES, FL_STAT_LAST_RANGE_GROUPS, FL_STAT_LAST_CHECK_GROUPS, FL_STAT_
 CV_STAT_LAUNCHES, CV_STAT_LAST_PRODUCT_GROUPS, CV_STAT_LAST_CHECK_GROUPS, CV_STAT_BLOCK_EDGE, CV_STAT_TRIP_FRAMES, CV_STAT_BLOCKS = 1, 2, 3, 4, 5, 6
 CV_MASS_WEIGHTED = 1
 CV_MAX_ATOMS = 4096
+MSD_X, MSD_Y, MSD_Z, MSD_NOJUMP = 1, 2, 4, 8
+MSD_MAX_PANEL_BYTES = 17179869184
+MSD_STAT_LAUNCHES, MSD_STAT_LAST_WALK_GROUPS, MSD_STAT_LAST_GRAM_GROUPS, MSD_STAT_BLOCK_EDGE, MSD_STAT_TRIP_VALUES = 1, 2, 3, 4, 5
+MSD_STAT_LAST_BLOCKS, MSD_STAT_LAGS, MSD_STAT_N_PAD, MSD_STAT_COUNTED = 6, 7, 8, 9
 CT_MAX_BINS = 4096
 MAX_SHAPES = 8
 
@@ -223,6 +227,19 @@ SIGNATURES = {
     "gr_covar_merge": (C.c_int, [C.c_void_p, C.c_void_p]),
     "gr_covar_set_launch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
     "gr_covar_stat": (C.c_int, [C.c_void_p, C.c_int, c_u64p]),
+    "gr_msd_create": (C.c_void_p, [C.c_void_p, C.c_char_p, C.c_uint32, C.c_uint32, c_i32p]),
+    "gr_msd_destroy": (None, [C.c_void_p]),
+    "gr_msd_append_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "gr_msd_clear": (C.c_int, [C.c_void_p]),
+    "gr_msd_frames": (C.c_uint64, [C.c_void_p]),
+    "gr_msd_n_atoms": (C.c_uint64, [C.c_void_p]),
+    "gr_msd_capacity": (C.c_uint64, [C.c_void_p]),
+    "gr_msd_compute": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "gr_msd_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gr_msd_read_from_origin": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gr_msd_read_displacements": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "gr_msd_set_launch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
+    "gr_msd_stat": (C.c_int, [C.c_void_p, C.c_int, c_u64p]),
     "gr_group_center_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "gr_group_translate_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_void_p, C.c_void_p]),
     "gr_group_wrap_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_void_p]),

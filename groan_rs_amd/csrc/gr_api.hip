@@ -3736,3 +3736,4 @@ int gr_synth_uniform(gr_ctx *c, uint32_t slot, const float *box9, uint64_t seed)
 #include "gr_rmsd_panel.h" // RMSDPanel: packed centred frames and their all-pairs RMSD matrix (f64 MFMA product): kernels, object and C ABI
 #include "gr_fluct.h"    // Fluctuations: mean structure and per-atom RMSF accumulated over batches of resident frames: kernels, object and C ABI
 #include "gr_covar.h"    // Covariance: positional covariance matrix and DCCM accumulated over batches of resident frames (f64 MFMA rank-K update): kernels, object and C ABI
+#include "gr_msd.h"      // MSD: nojump unwrapping and the windowed mean-squared displacement over resident frames (f64 MFMA Gram product): kernels, object and C ABI

@@ -46,6 +46,7 @@ typedef struct gr_contacts gr_contacts;
 typedef struct gr_rmsd_panel gr_rmsd_panel;
 typedef struct gr_fluct gr_fluct;
 typedef struct gr_covar gr_covar;
+typedef struct gr_msd gr_msd;
 typedef struct gr_xtc gr_xtc;
 
 /* status codes; 1..7 map onto the reference's error enums (src/errors.rs) */
@@ -947,6 +948,80 @@ int gr_covar_read_dccm(gr_covar *cv, double *corr /* [S][S] */);
 int gr_covar_merge(gr_covar *dst, gr_covar *src);
 int gr_covar_set_launch(gr_covar *cv, uint32_t product_groups, uint32_t check_groups);   /* 0: default; the result never depends on it */
 int gr_covar_stat(const gr_covar *cv, int key, uint64_t *value);
+
+/* ---------------------------------------------------------------- MSD: nojump unwrapping and windowed mean-squared displacement
+ * The first dynamical analysis (diffusion of lipids, water, ions; gmx msd); the reference has no function for it.  For a snapshot of a
+ * group's S atoms (group order, padded with zeros to n_pad, a multiple of 64) the object keeps per atom the ORIGIN o (f32 x3: the
+ * position in the first counted frame), w (f32 x3: the position as stored in the last counted frame) and u (f64 x3: the unwrapped
+ * position in the last counted frame), and a PANEL X[capacity][3][n_pad] (f32, component-major): row t is frame t's displacement from
+ * the origin; components not selected by the flags are stored as zeros (the unwrapping itself is always 3-D).  With it q[t], the sum of
+ * the row's squares (f64), and ok[t].  Once appended, a frame's slot may be overwritten: a trajectory longer than the slots is appended
+ * block by block.
+ * THE RULE, per atom, for one good frame with stored position x and box B:
+ *   first counted frame:  o = w = x, u = (double)x
+ *   otherwise:            d = x - w, ONE f32 subtraction per component.  With GR_MSD_NOJUMP d is reduced along c, then b, then a:
+ *                         k = rint(d * (1/L)) corrected by +-1 where the remainder lies beyond +-L/2, then d = fmaf(-k, box vector, d)
+ *                         (the brick reduction of the library's minimum image, no candidate-table refinement; the box is the frame's
+ *                         own); u += (double)d, a sequential f64 chain; w = x.  Without NOJUMP u = (double)x.
+ *   panel entry:          (float)(u - (double)o), or 0 for a component that is not selected
+ * This sums displacements, so it stays correct when the box changes from frame to frame.  A step of half a box edge or more between
+ * two counted frames is ambiguous by nature and is taken as the shorter way round.  Removing centre-of-mass drift is the caller's
+ * (translate or fit the frames first); the slots are never written.
+ * ORDER OF THE SUMS.  A lane owns its atom for a launch and takes the frames in ascending order; nothing is split over frames, no atomic
+ * is used: o, w, u, the panel and q are a function of the SEQUENCE of appended frames alone -- not of how they were cut into calls,
+ * 1024-frame segments or grids.  gr_msd_compute forms G = X X^T on the f64 matrix cores (f32 operands widened: exact products, f64
+ * sums) for the 64 x 64 blocks of frame pairs on and above the diagonal that touch the band t' - t <= max_lag; an entry belongs to one
+ * wave and is one chain over the 3 n_pad values of its rows in ascending trips: its bits depend on its two rows and n_pad alone.
+ * D2(t, t') = q_t + q_t' - 2 G(t, t') for t < t' (f64 is required: after a long walk q_t is t times larger than D2(t, t + 1));
+ * D2(t, t) IS DEFINED AS 0, so msd[0] is exactly 0.  The entries of one diagonal of a block are added in ascending row order, the blocks'
+ * partial sums of a lag in ascending block-row order; no atomic decides a sum.  So sum[tau] is a function of the panel alone, the same
+ * bits for every max_lag >= tau, grid and context.  Per pair |D2 - exact| <= (2 K + 4) 2^-53 (q_t + q_t'), K = 3 n_pad.
+ * NOT promised: the bits of G, and so of the sums, on another device generation or for another n_pad -- the four values one matrix
+ * instruction adds are added in an order the hardware does not document (tests pin that equal rows give equal entries wherever they lie) --
+ * and more than the bound above against a direct evaluation of sum |d_t - d_t'|^2.
+ *   gr_msd_create             snapshots the group's atoms.  flags: at least one of GR_MSD_X | GR_MSD_Y | GR_MSD_Z (XY: the lateral MSD of
+ *                             a membrane), optionally GR_MSD_NOJUMP; anything else, capacity 0, or capacity x 3 x n_pad x 4 B above
+ *                             GR_MSD_MAX_PANEL_BYTES: GR_E_INVALID_ARG.  GR_E_GROUP_NOT_FOUND, GR_E_EMPTY_GROUP; GR_E_HIP when the allocation fails.
+ *   gr_msd_append_batch       appends the n_frames slots from first_slot as time indices frames() .. frames() + n_frames - 1.  Frame
+ *                             handling is Fluctuations': a frame in which an atom of the snapshot has no position fails with
+ *                             GR_E_NO_POSITION (gr_last_error_index = the lowest such atom); with NOJUMP a frame without a (usable) box
+ *                             fails with the box error.  A FAILED FRAME STILL TAKES A TIME INDEX: its row is zeros, its ok 0, it enters
+ *                             no pair; the walk skips it and the next good frame is unwrapped against the last good one.  Batch rules:
+ *                             status_out[f] is each frame's status, the return value, message and index are the first failed frame's,
+ *                             a hard error writes nothing.  Beyond the capacity: GR_E_INVALID_ARG, nothing is changed.
+ *   gr_msd_compute            the band up to max_lag (a max_lag beyond frames() - 1 is CLAMPED to it); no frame appended: GR_E_INVALID_ARG
+ *   gr_msd_read               msd[tau] = sum[tau] / (pairs[tau] * S), tau = 0 .. the computed max_lag (GR_MSD_STAT_LAGS values), closed in
+ *                             f64; NaN where pairs[tau] == 0; pairs[tau] counts the t with ok[t] and ok[t + tau].  Each may be NULL.
+ *                             Before gr_msd_compute, or after an append or clear behind it: GR_E_INVALID_ARG.
+ *   gr_msd_read_from_origin   out[t] = q[t] / S for t < frames(): the MSD from the first counted frame; NaN for a failed frame
+ *   gr_msd_read_displacements out[nt][S][3] (f32): rows t0 .. t0 + nt - 1 of the panel in group order
+ *   gr_msd_frames             time indices taken (failed frames included);  gr_msd_n_atoms;  gr_msd_capacity
+ *   gr_msd_clear              forgets every frame (and the origin)
+ *   gr_msd_set_launch         test hook: the number of ranges of the walk and a cap on the grid of the product (0: one wave per 64
+ *                             atoms / one workgroup per block).  The result never depends on it.
+ *   gr_msd_stat               GR_MSD_STAT_*: launches so far, the grids of the last walk and product, the edge of a block in frames, the
+ *                             panel values per trip, the blocks of the last compute, its lags, n_pad, the counted frames
+ * The object keeps a pointer to its context: destroy it first. */
+#define GR_MSD_X 1u
+#define GR_MSD_Y 2u
+#define GR_MSD_Z 4u
+#define GR_MSD_NOJUMP 8u
+#define GR_MSD_MAX_PANEL_BYTES 17179869184u      /* 16 GiB of panel at most */
+enum { GR_MSD_STAT_LAUNCHES = 1, GR_MSD_STAT_LAST_WALK_GROUPS = 2, GR_MSD_STAT_LAST_GRAM_GROUPS = 3, GR_MSD_STAT_BLOCK_EDGE = 4, GR_MSD_STAT_TRIP_VALUES = 5,
+       GR_MSD_STAT_LAST_BLOCKS = 6, GR_MSD_STAT_LAGS = 7, GR_MSD_STAT_N_PAD = 8, GR_MSD_STAT_COUNTED = 9 };
+gr_msd *gr_msd_create(gr_ctx *ctx, const char *group, uint32_t capacity_frames, uint32_t flags, int *status);
+void gr_msd_destroy(gr_msd *m);
+int gr_msd_append_batch(gr_msd *m, uint32_t first_slot, uint32_t n_frames, int *status_out /* [n_frames] or NULL */);
+int gr_msd_clear(gr_msd *m);
+uint64_t gr_msd_frames(const gr_msd *m);
+uint64_t gr_msd_n_atoms(const gr_msd *m);
+uint64_t gr_msd_capacity(const gr_msd *m);
+int gr_msd_compute(gr_msd *m, uint32_t max_lag);
+int gr_msd_read(gr_msd *m, double *msd /* [lags] */, uint64_t *pairs /* [lags] */);
+int gr_msd_read_from_origin(gr_msd *m, double *out /* [frames] */);
+int gr_msd_read_displacements(gr_msd *m, uint32_t t0, uint32_t nt, float *out /* [nt][S][3] */);
+int gr_msd_set_launch(gr_msd *m, uint32_t walk_groups, uint32_t gram_groups);   /* 0: default; the result never depends on it */
+int gr_msd_stat(const gr_msd *m, int key, uint64_t *value);
 
 /* ---------------------------------------------------------------- xtc reader (host side)
  * The stage in front of the path: XtcReader (src/io/xtc_io/mod.rs, molly_xtc.rs:96-308, xdrfile_xtc.rs:42-104).

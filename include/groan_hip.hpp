@@ -1163,4 +1163,67 @@ class Covariance {
     gr_covar *f_ = nullptr;
 };
 
+// ---- Msd: "nojump" unwrapping and the windowed mean-squared displacement of a group over blocks of resident frames (diffusion; the
+// reference has no function for it).  append() takes frames as time indices -- a failed frame still takes one and enters no pair --,
+// msd(max_lag) closes the band of lags.  Displacements, q and the sums are a function of the sequence of appended frames alone.
+class Msd {
+  public:
+    struct Curve { std::vector<double> msd; std::vector<uint64_t> pairs; };     // [lags] each; msd is NaN where pairs is 0
+
+    Msd(System &system, const std::string &group, uint32_t capacity_frames, uint32_t flags = GR_MSD_X | GR_MSD_Y | GR_MSD_Z | GR_MSD_NOJUMP) : ctx_(system.raw()) {
+        int st = 0;
+        f_ = gr_msd_create(ctx_, group.c_str(), capacity_frames, flags, &st);
+        if (!f_) raise(st);
+    }
+    ~Msd() { if (f_) gr_msd_destroy(f_); }
+    Msd(const Msd &) = delete;
+    Msd &operator=(const Msd &) = delete;
+    Msd(Msd &&o) noexcept : ctx_(o.ctx_), f_(o.f_) { o.f_ = nullptr; }
+
+    uint64_t frames() const { return gr_msd_frames(f_); }
+    uint64_t n_atoms() const { return gr_msd_n_atoms(f_); }
+    uint64_t capacity() const { return gr_msd_capacity(f_); }
+    // appends n_frames slots from first_slot; a failed frame takes a time index and enters no pair; throws the first failure unless
+    // `status` is given.  A refused call (beyond the capacity, slots out of range) always throws
+    void append(uint32_t first_slot, uint32_t n_frames, std::vector<int> *status = nullptr) {
+        std::vector<int> st(n_frames);
+        const int r = gr_msd_append_batch(f_, first_slot, n_frames, st.data());
+        detail::batch_status(r, st, status, [this](int e) { raise(e); });
+    }
+    void clear() { check(gr_msd_clear(f_)); }
+    // the curve for lags 0 .. max_lag (clamped to frames() - 1)
+    Curve msd(uint32_t max_lag = 0xFFFFFFFFu) {
+        check(gr_msd_compute(f_, max_lag));
+        Curve c;
+        const size_t lags = (size_t)stat(GR_MSD_STAT_LAGS);
+        c.msd.resize(lags); c.pairs.resize(lags);
+        check(gr_msd_read(f_, c.msd.data(), c.pairs.data()));
+        return c;
+    }
+    std::vector<double> from_origin() { std::vector<double> o(frames()); if (!o.empty()) check(gr_msd_read_from_origin(f_, o.data())); return o; }
+    // [nt][S][3]: rows t0 .. t0 + nt - 1 of the panel in group order
+    std::vector<float> displacements(uint32_t t0, uint32_t nt) {
+        std::vector<float> d((size_t)nt * 3 * n_atoms());
+        check(gr_msd_read_displacements(f_, t0, nt, d.data()));
+        return d;
+    }
+    void set_launch(uint32_t walk_groups, uint32_t gram_groups) { gr_msd_set_launch(f_, walk_groups, gram_groups); }
+    uint64_t stat(int key) const { uint64_t v = 0; if (gr_msd_stat(f_, key, &v) != GR_OK) throw std::invalid_argument("Msd::stat | unknown key"); return v; }
+    gr_msd *raw_handle() const { return f_; }
+
+  private:
+    void check(int st) const { if (st != GR_OK) raise(st); }
+    [[noreturn]] void raise(int st) const {
+        switch (st) {
+        case GR_E_GROUP_NOT_FOUND: throw Error("GroupError", "NotFound", st);
+        case GR_E_EMPTY_GROUP: throw Error("GroupError", "EmptyGroup", st);
+        case GR_E_NO_POSITION: throw Error("GroupError", "InvalidPosition", st, gr_last_error_index(ctx_));
+        case GR_E_NO_BOX: throw Error("SimBoxError", "DoesNotExist", st);
+        default: throw Error("DeviceError", std::string(gr_status_string(st)) + ": " + gr_last_error(ctx_), st);
+        }
+    }
+    gr_ctx *ctx_ = nullptr;
+    gr_msd *f_ = nullptr;
+};
+
 }  // namespace groan

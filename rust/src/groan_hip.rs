@@ -66,6 +66,19 @@ pub const GR_CT_STAT_LAST_CELLS: c_int = 6;
 pub const GR_CT_STAT_LAST_RUN_CELLS_MIN: c_int = 7;
 pub const GR_CT_STAT_LAST_RUN_CELLS_MAX: c_int = 8;
 pub const GR_CT_STAT_LAST_WALK_GROUPS: c_int = 9;
+pub const GR_MSD_X: u32 = 1;
+pub const GR_MSD_Y: u32 = 2;
+pub const GR_MSD_Z: u32 = 4;
+pub const GR_MSD_NOJUMP: u32 = 8;
+pub const GR_MSD_STAT_LAUNCHES: c_int = 1;
+pub const GR_MSD_STAT_LAST_WALK_GROUPS: c_int = 2;
+pub const GR_MSD_STAT_LAST_GRAM_GROUPS: c_int = 3;
+pub const GR_MSD_STAT_BLOCK_EDGE: c_int = 4;
+pub const GR_MSD_STAT_TRIP_VALUES: c_int = 5;
+pub const GR_MSD_STAT_LAST_BLOCKS: c_int = 6;
+pub const GR_MSD_STAT_LAGS: c_int = 7;
+pub const GR_MSD_STAT_N_PAD: c_int = 8;
+pub const GR_MSD_STAT_COUNTED: c_int = 9;
 
 #[repr(C)] pub struct gr_hbond_plan { _private: [u8; 0] }
 #[repr(C)] pub struct gr_gridmap { _private: [u8; 0] }
@@ -75,6 +88,7 @@ pub const GR_CT_STAT_LAST_WALK_GROUPS: c_int = 9;
 #[repr(C)] pub struct gr_rmsd_panel { _private: [u8; 0] }
 #[repr(C)] pub struct gr_fluct { _private: [u8; 0] }
 #[repr(C)] pub struct gr_covar { _private: [u8; 0] }
+#[repr(C)] pub struct gr_msd { _private: [u8; 0] }
 #[repr(C)] pub struct gr_pool { _private: [u8; 0] }
 #[repr(C)] pub struct gr_comm { _private: [u8; 0] }
 /// `body(ctx, worker, frame, user, result)` of gr_pool_map: non-zero return = the frame's error (the first one wins)
@@ -259,6 +273,20 @@ extern "C" {
     pub fn gr_covar_merge(dst: *mut gr_covar, src: *mut gr_covar) -> c_int;
     pub fn gr_covar_set_launch(cv: *mut gr_covar, product_groups: u32, check_groups: u32) -> c_int;
     pub fn gr_covar_stat(cv: *const gr_covar, key: c_int, value: *mut u64) -> c_int;
+    // MSD: nojump unwrapping and the windowed mean-squared displacement of a group over resident frames (flags: GR_MSD_X | _Y | _Z, GR_MSD_NOJUMP; status_out, msd and pairs may be null)
+    pub fn gr_msd_create(ctx: *mut gr_ctx, group: *const c_char, capacity_frames: u32, flags: u32, status: *mut c_int) -> *mut gr_msd;
+    pub fn gr_msd_destroy(m: *mut gr_msd);
+    pub fn gr_msd_append_batch(m: *mut gr_msd, first_slot: u32, n_frames: u32, status_out: *mut c_int) -> c_int;
+    pub fn gr_msd_clear(m: *mut gr_msd) -> c_int;
+    pub fn gr_msd_frames(m: *const gr_msd) -> u64;
+    pub fn gr_msd_n_atoms(m: *const gr_msd) -> u64;
+    pub fn gr_msd_capacity(m: *const gr_msd) -> u64;
+    pub fn gr_msd_compute(m: *mut gr_msd, max_lag: u32) -> c_int;
+    pub fn gr_msd_read(m: *mut gr_msd, msd: *mut f64, pairs: *mut u64) -> c_int;
+    pub fn gr_msd_read_from_origin(m: *mut gr_msd, out: *mut f64) -> c_int;
+    pub fn gr_msd_read_displacements(m: *mut gr_msd, t0: u32, nt: u32, out: *mut c_float) -> c_int;
+    pub fn gr_msd_set_launch(m: *mut gr_msd, walk_groups: u32, gram_groups: u32) -> c_int;
+    pub fn gr_msd_stat(m: *const gr_msd, key: c_int, value: *mut u64) -> c_int;
     pub fn gr_ctx_set_tuning(ctx: *mut gr_ctx, key: c_int, value: i64) -> c_int;   // GR_TUNE_* (include/groan_hip.h)
     pub fn gr_host_alloc(bytes: usize) -> *mut c_void;                              // pinned memory: asynchronous gr_frame_upload
     pub fn gr_host_free(p: *mut c_void);
