@@ -37,6 +37,10 @@ MSD_X, MSD_Y, MSD_Z, MSD_NOJUMP = 1, 2, 4, 8
 MSD_MAX_PANEL_BYTES = 17179869184
 MSD_STAT_LAUNCHES, MSD_STAT_LAST_WALK_GROUPS, MSD_STAT_LAST_GRAM_GROUPS, MSD_STAT_BLOCK_EDGE, MSD_STAT_TRIP_VALUES = 1, 2, 3, 4, 5
 MSD_STAT_LAST_BLOCKS, MSD_STAT_LAGS, MSD_STAT_N_PAD, MSD_STAT_COUNTED = 6, 7, 8, 9
+IC_DISTANCE, IC_ANGLE, IC_DIHEDRAL, IC_AXIS = 1, 2, 3, 4
+IC_PBC = 1
+IC_MAX_WS_BYTES = 64 << 20
+IC_STAT_LAUNCHES, IC_STAT_LAST_RANGE_GROUPS, IC_STAT_LAST_FRAME_GROUPS, IC_STAT_LAST_CHECK_GROUPS, IC_STAT_ARITY, IC_STAT_UNIQUE_ATOMS, IC_STAT_AHEAD = 1, 2, 3, 4, 5, 6, 7
 CT_MAX_BINS = 4096
 MAX_SHAPES = 8
 
@@ -240,6 +244,19 @@ SIGNATURES = {
     "gr_msd_read_displacements": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     "gr_msd_set_launch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
     "gr_msd_stat": (C.c_int, [C.c_void_p, C.c_int, c_u64p]),
+    "gr_internals_create": (C.c_void_p, [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, c_i32p]),
+    "gr_internals_destroy": (None, [C.c_void_p]),
+    "gr_internals_count": (C.c_uint64, [C.c_void_p]),
+    "gr_internals_frames": (C.c_uint64, [C.c_void_p]),
+    "gr_internals_values_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "gr_internals_values_batch_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "gr_internals_accumulate_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "gr_internals_clear": (C.c_int, [C.c_void_p]),
+    "gr_internals_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gr_internals_read_raw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_u64p]),
+    "gr_internals_merge": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gr_internals_set_launch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
+    "gr_internals_stat": (C.c_int, [C.c_void_p, C.c_int, c_u64p]),
     "gr_group_center_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "gr_group_translate_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_void_p, C.c_void_p]),
     "gr_group_wrap_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_void_p]),

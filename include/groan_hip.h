@@ -47,6 +47,7 @@ typedef struct gr_rmsd_panel gr_rmsd_panel;
 typedef struct gr_fluct gr_fluct;
 typedef struct gr_covar gr_covar;
 typedef struct gr_msd gr_msd;
+typedef struct gr_internals gr_internals;
 typedef struct gr_xtc gr_xtc;
 
 /* status codes; 1..7 map onto the reference's error enums (src/errors.rs) */
@@ -1022,6 +1023,86 @@ int gr_msd_read_from_origin(gr_msd *m, double *out /* [frames] */);
 int gr_msd_read_displacements(gr_msd *m, uint32_t t0, uint32_t nt, float *out /* [nt][S][3] */);
 int gr_msd_set_launch(gr_msd *m, uint32_t walk_groups, uint32_t gram_groups);   /* 0: default; the result never depends on it */
 int gr_msd_stat(const gr_msd *m, int key, uint64_t *value);
+
+/* ---------------------------------------------------------------- Internals: distance, angle and dihedral series over resident frames
+ * "What is this bond length, this angle or this torsion in every frame?" -- Ramachandran maps, side-chain chi angles, distance and angle
+ * series between picked atoms, lipid order parameters.  The reference has Vector3D::angle (vector3d.rs:276-278) and distance only: no
+ * dihedral and no per-tuple series.  The object holds a fixed list of T atom tuples of one kind and gives, for a block of resident frames,
+ * either the value of every tuple in every frame (values) or running per-tuple statistics over any number of calls (accumulate: mean and
+ * variance, which for the axis kind is the order parameter) without storing the series.
+ * DEFINITIONS.  Displacement d(a->b) = x_b - x_a, one f32 subtraction per component.  With the flag GR_IC_PBC it is followed by
+ * gr_min_image_vec with the frame's own box (orthorhombic and triclinic).  Without the flag the raw difference stands and a frame needs no
+ * box.  Angles are in RADIANS, as Vector3D::angle gives them.
+ *   GR_IC_DISTANCE  (i, j)                     gr_mag3(d(i->j)), nm
+ *   GR_IC_ANGLE     (i, j, k), vertex j        u = d(j->i), v = d(j->k): atan2f(|u x v|, u.v) in [0, pi]
+ *   GR_IC_DIHEDRAL  (i, j, k, l)               b1 = d(i->j), b2 = d(j->k), b3 = d(k->l), n1 = b1 x b2, n2 = b2 x b3:
+ *                                              atan2f(|b2| (b1.n2), n1.n2) in [-pi, pi]
+ *   GR_IC_AXIS      (i, j) + a unit vector a   cos theta = (d(i->j).a) / |d(i->j)|; 0 when |d| = 0
+ * THE PINS of the dihedral's sign, with i = (0,1,0), j = (0,0,0), k = (1,0,0): l = (1,0,1) gives +pi/2, l = (1,1,0) gives 0 (cis),
+ * l = (1,-1,0) gives pi (trans), l = (1,0,-1) gives -pi/2 (the IUPAC sign, as gmx angle and MDAnalysis have it).  The formula and the
+ * pins are the definition.  atan2f instead of the reference's acos(dot / (|u||v|)): it stays well conditioned near 0 and pi; the
+ * reference's known answers for `angle` come out within 4 ulp(pi).  Every product and sum of these formulas is rounded on its own.
+ * Degenerate geometry never produces NaN: coincident atoms give atan2f(0, 0) = 0, a collinear dihedral some finite value in [-pi, pi].
+ * STATISTICS.  Per tuple the object keeps an ORIGIN o (f32): the tuple's value in the first frame the object ever counted; and in f64
+ * s = sum d and q = sum d * d with d = v - o, ONE f32 subtraction.  THE DIHEDRAL'S WRAP RULE: for GR_IC_DIHEDRAL only, d is reduced once
+ * in f32 with PI_F = (float)M_PI: if d > PI_F, subtract 2 PI_F; else if d < -PI_F, add 2 PI_F.  A torsion that oscillates across +-pi
+ * therefore has a small variance and a mean near +-pi; THIS HOLDS WHILE THE DISTRIBUTION STAYS WITHIN pi OF THE ORIGIN.
+ * ORDER OF THE SUMS.  A lane owns its tuple for a launch and adds the frames in ascending order, one after another, as a single f64
+ * chain; nothing is split over frames and no atomic touches a sum.  v in accumulate is the same bits values gives for that frame and
+ * tuple.  So o, s, q are a function of the SEQUENCE of counted frames alone -- not of how they were cut into calls, 1024-frame segments
+ * or grids -- and tests/internals_ref.py restates them from the rows values returns (f32 subtract, f32 wrap, f64 cumulative add in frame
+ * order), bit for bit.
+ *   gr_internals_create              atoms: [T][arity] row-major (arity 2, 3, 4, 2), copied.  flags: GR_IC_PBC or 0.  axis: [3] for
+ *                                    GR_IC_AXIS (normalised on the host in f64, then rounded to f32), else NULL.  An atom index >= n_atoms:
+ *                                    GR_E_OUT_OF_RANGE + gr_last_error_index = that index.  GR_E_INVALID_ARG: an unknown kind or flag,
+ *                                    T = 0, an atom that appears twice in one tuple (gr_last_error_index = the tuple); for GR_IC_AXIS a
+ *                                    NULL, zero or non-finite axis.  The host keeps the sorted list of unique atoms the tuples name.
+ *   gr_internals_count               T;  gr_internals_frames: frames counted by accumulate
+ *   gr_internals_values_batch        out[f][t] (host, [n_frames][T]) for the n_frames slots from first_slot.  Per frame: with GR_IC_PBC the
+ *                                    box checks (GR_E_NO_BOX / the slot's box status / GR_E_NOT_ORTHOGONAL in strict mode), then a frame in
+ *                                    which any atom named by any tuple has no position fails with GR_E_NO_POSITION, gr_last_error_index =
+ *                                    the lowest such atom; an atom without position that no tuple names fails nothing.  A FAILED FRAME IS
+ *                                    A ROW OF NaN, the other rows are untouched by it.  Batch rules: status_out[f] is each frame's status,
+ *                                    the return value, message and index are the first failed frame's, a hard error writes nothing.
+ *                                    The device variant runs into a grow-only workspace of at most GR_IC_MAX_WS_BYTES per piece of a
+ *                                    segment; no result depends on the piece.
+ *   gr_internals_values_batch_device the same into device memory of the context's device: row f starts f * ld floats in, ld >= T (else
+ *                                    GR_E_INVALID_ARG); the floats of a row beyond T are not written
+ *   gr_internals_accumulate_batch    counts the frames; a failed frame (as above) is counted for NO tuple; when the first frame fails the
+ *                                    origin comes from the first frame that is counted.  Nothing is stored per frame.
+ *   gr_internals_clear               forgets every frame (and the origin)
+ *   gr_internals_read                closes on the host in f64: mean = o + s / n, var = max(q - s^2 / n, 0) / n; a dihedral's mean is
+ *                                    brought back into (-pi, pi].  Each may be NULL.  n = 0: GR_E_INVALID_ARG.
+ *   gr_internals_read_raw            o, s, q as they stand ([T] each) and n; each may be NULL
+ *   gr_internals_merge               adds src's frames to dst after moving its sums to dst's origin in f64, delta = o_src - o_dst (a
+ *                                    dihedral's delta is wrapped into (-pi, pi]): s += s_src + n_src delta, q += q_src + 2 delta s_src +
+ *                                    n_src delta^2.  An empty src changes nothing, an empty dst takes src's state as it is.
+ *                                    GR_E_INCONSISTENT_GROUP if kind, flags, axis, T or the tuples differ; dst == src: GR_E_INVALID_ARG.
+ *                                    AFTER A MERGE THE SUMS ARE NO LONGER THOSE OF ONE WALK.
+ *   gr_internals_set_launch          test hook: the ranges the tuples are cut into (one wave each; 0: one per 64 tuples) and the frames
+ *                                    of one workgroup of values (0: chosen from T and the number of frames).  No result depends on it.
+ *   gr_internals_stat                GR_IC_STAT_*: launches so far, the grids of the last launch (tuple ranges, frame chunks, position
+ *                                    check), the arity, the unique atoms, the frames a lane has in flight
+ * The object keeps a pointer to its context: destroy it first. */
+#define GR_IC_PBC 1u
+#define GR_IC_MAX_WS_BYTES (64u << 20)     /* the device workspace of gr_internals_values_batch at most: 64 MiB */
+enum { GR_IC_DISTANCE = 1, GR_IC_ANGLE = 2, GR_IC_DIHEDRAL = 3, GR_IC_AXIS = 4 };
+enum { GR_IC_STAT_LAUNCHES = 1, GR_IC_STAT_LAST_RANGE_GROUPS = 2, GR_IC_STAT_LAST_FRAME_GROUPS = 3, GR_IC_STAT_LAST_CHECK_GROUPS = 4, GR_IC_STAT_ARITY = 5,
+       GR_IC_STAT_UNIQUE_ATOMS = 6, GR_IC_STAT_AHEAD = 7 };
+gr_internals *gr_internals_create(gr_ctx *ctx, int kind, const uint64_t *atoms /* [T][arity], row-major */, uint64_t n_tuples,
+                                  uint32_t flags /* GR_IC_PBC */, const float *axis /* [3], GR_IC_AXIS only, else NULL */, int *status);
+void gr_internals_destroy(gr_internals *ic);
+uint64_t gr_internals_count(const gr_internals *ic);          /* T */
+uint64_t gr_internals_frames(const gr_internals *ic);         /* frames counted by accumulate */
+int gr_internals_values_batch(gr_internals *ic, uint32_t first_slot, uint32_t n_frames, float *out /* host [n_frames][T] */, int *status_out);
+int gr_internals_values_batch_device(gr_internals *ic, uint32_t first_slot, uint32_t n_frames, float *out_dev, uint64_t ld /* floats per row, >= T */, int *status_out);
+int gr_internals_accumulate_batch(gr_internals *ic, uint32_t first_slot, uint32_t n_frames, int *status_out);
+int gr_internals_clear(gr_internals *ic);
+int gr_internals_read(gr_internals *ic, double *mean /* [T] */, double *var /* [T] */);
+int gr_internals_read_raw(gr_internals *ic, float *origin /* [T] */, double *sum /* [T] */, double *sumsq /* [T] */, uint64_t *n);
+int gr_internals_merge(gr_internals *dst, gr_internals *src);
+int gr_internals_set_launch(gr_internals *ic, uint32_t tuple_ranges, uint32_t frame_chunk);   /* test hook, 0: default; no result depends on it */
+int gr_internals_stat(const gr_internals *ic, int key, uint64_t *value);
 
 /* ---------------------------------------------------------------- xtc reader (host side)
  * The stage in front of the path: XtcReader (src/io/xtc_io/mod.rs, molly_xtc.rs:96-308, xdrfile_xtc.rs:42-104).

@@ -1226,4 +1226,84 @@ class Msd {
     gr_msd *f_ = nullptr;
 };
 
+// ---- Internals: the distance, angle, dihedral or axis cosine of a fixed list of atom tuples in every frame of a block of resident
+// frames (values), or their running mean and variance over any number of calls (accumulate); the reference has Vector3D::angle and
+// distance only.  Angles in radians, the dihedral's sign is IUPAC's (groan_hip.h has the definitions).  The sums are added frame after
+// frame, so they do not depend on how the frames were cut into calls; after merge() they are no longer those of one walk.
+class Internals {
+  public:
+    struct Raw { std::vector<float> origin; std::vector<double> sum, sumsq; uint64_t n = 0; };    // [T] each
+    struct Stats { std::vector<double> mean, var; };                                             // [T] each
+
+    // tuples: [T][arity] row-major (arity 2, 3, 4, 2 for GR_IC_DISTANCE, _ANGLE, _DIHEDRAL, _AXIS); axis: GR_IC_AXIS only
+    Internals(System &system, int kind, const std::vector<uint64_t> &tuples, uint32_t flags = GR_IC_PBC, const float *axis = nullptr) : ctx_(system.raw()) {
+        const uint64_t arity = kind == GR_IC_ANGLE ? 3 : (kind == GR_IC_DIHEDRAL ? 4 : 2);
+        int st = 0;
+        f_ = gr_internals_create(ctx_, kind, tuples.data(), tuples.size() / arity, flags, axis, &st);
+        if (!f_) raise(st);
+    }
+    ~Internals() { if (f_) gr_internals_destroy(f_); }
+    Internals(const Internals &) = delete;
+    Internals &operator=(const Internals &) = delete;
+    Internals(Internals &&o) noexcept : ctx_(o.ctx_), f_(o.f_) { o.f_ = nullptr; }
+
+    uint64_t count() const { return gr_internals_count(f_); }
+    uint64_t frames() const { return gr_internals_frames(f_); }
+    // [n_frames][T]; a failed frame is a row of NaN and throws the first failure unless `status` is given.  A refused call always throws
+    std::vector<float> values(uint32_t first_slot, uint32_t n_frames, std::vector<int> *status = nullptr) {
+        std::vector<int> st(n_frames);
+        std::vector<float> out((size_t)n_frames * count() + 1);
+        const int r = gr_internals_values_batch(f_, first_slot, n_frames, out.data(), st.data());
+        detail::batch_status(r, st, status, [this](int e) { raise(e); });
+        out.resize((size_t)n_frames * count());
+        return out;
+    }
+    // the same into device memory: row f starts f * ld floats in (ld >= T)
+    void values_device(uint32_t first_slot, uint32_t n_frames, float *out_dev, uint64_t ld, std::vector<int> *status = nullptr) {
+        std::vector<int> st(n_frames);
+        const int r = gr_internals_values_batch_device(f_, first_slot, n_frames, out_dev, ld, st.data());
+        detail::batch_status(r, st, status, [this](int e) { raise(e); });
+    }
+    // counts n_frames slots from first_slot; a failed frame is counted for no tuple
+    void accumulate(uint32_t first_slot, uint32_t n_frames, std::vector<int> *status = nullptr) {
+        std::vector<int> st(n_frames);
+        const int r = gr_internals_accumulate_batch(f_, first_slot, n_frames, st.data());
+        detail::batch_status(r, st, status, [this](int e) { raise(e); });
+    }
+    void clear() { check(gr_internals_clear(f_)); }
+    // mean and variance (divided by n) per tuple; throws before the first counted frame
+    Stats read() { Stats s; s.mean.resize(count()); s.var.resize(count()); check(gr_internals_read(f_, s.mean.data(), s.var.data())); return s; }
+    Raw raw() {
+        Raw r;
+        r.origin.resize(count()); r.sum.resize(count()); r.sumsq.resize(count());
+        check(gr_internals_read_raw(f_, r.origin.data(), r.sum.data(), r.sumsq.data(), &r.n));
+        return r;
+    }
+    // S = 1/2 <3 cos^2 - 1> per tuple (GR_IC_AXIS)
+    std::vector<double> order_parameter() {
+        const Stats s = read();
+        std::vector<double> p(s.mean.size());
+        for (size_t t = 0; t < p.size(); ++t) p[t] = 1.5 * (s.var[t] + s.mean[t] * s.mean[t]) - 0.5;
+        return p;
+    }
+    void merge(Internals &src) { check(gr_internals_merge(f_, src.f_)); }
+    void set_launch(uint32_t tuple_ranges, uint32_t frame_chunk) { gr_internals_set_launch(f_, tuple_ranges, frame_chunk); }
+    uint64_t stat(int key) const { uint64_t v = 0; if (gr_internals_stat(f_, key, &v) != GR_OK) throw std::invalid_argument("Internals::stat | unknown key"); return v; }
+    gr_internals *raw_handle() const { return f_; }
+
+  private:
+    void check(int st) const { if (st != GR_OK) raise(st); }
+    [[noreturn]] void raise(int st) const {
+        switch (st) {
+        case GR_E_OUT_OF_RANGE: throw Error("AtomError", "OutOfRange", st, gr_last_error_index(ctx_));
+        case GR_E_NO_POSITION: throw Error("AtomError", "InvalidPosition", st, gr_last_error_index(ctx_));
+        case GR_E_INCONSISTENT_GROUP: throw Error("GroupError", "InconsistentGroup", st);
+        case GR_E_NO_BOX: throw Error("SimBoxError", "DoesNotExist", st);
+        default: throw Error("DeviceError", std::string(gr_status_string(st)) + ": " + gr_last_error(ctx_), st);
+        }
+    }
+    gr_ctx *ctx_ = nullptr;
+    gr_internals *f_ = nullptr;
+};
+
 }  // namespace groan

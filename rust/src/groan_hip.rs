@@ -89,6 +89,7 @@ pub const GR_MSD_STAT_COUNTED: c_int = 9;
 #[repr(C)] pub struct gr_fluct { _private: [u8; 0] }
 #[repr(C)] pub struct gr_covar { _private: [u8; 0] }
 #[repr(C)] pub struct gr_msd { _private: [u8; 0] }
+#[repr(C)] pub struct gr_internals { _private: [u8; 0] }
 #[repr(C)] pub struct gr_pool { _private: [u8; 0] }
 #[repr(C)] pub struct gr_comm { _private: [u8; 0] }
 /// `body(ctx, worker, frame, user, result)` of gr_pool_map: non-zero return = the frame's error (the first one wins)
@@ -287,6 +288,20 @@ extern "C" {
     pub fn gr_msd_read_displacements(m: *mut gr_msd, t0: u32, nt: u32, out: *mut c_float) -> c_int;
     pub fn gr_msd_set_launch(m: *mut gr_msd, walk_groups: u32, gram_groups: u32) -> c_int;
     pub fn gr_msd_stat(m: *const gr_msd, key: c_int, value: *mut u64) -> c_int;
+    // Internals: distance (kind 1), angle (2), dihedral (3) and axis-cosine (4) series of atom tuples over resident frames and their running statistics (flags: GR_IC_PBC = 1; axis: 3 floats for kind 4, else null; status_out, mean, var, origin, sum, sumsq and n may be null)
+    pub fn gr_internals_create(ctx: *mut gr_ctx, kind: c_int, atoms: *const u64, n_tuples: u64, flags: u32, axis: *const c_float, status: *mut c_int) -> *mut gr_internals;
+    pub fn gr_internals_destroy(ic: *mut gr_internals);
+    pub fn gr_internals_count(ic: *const gr_internals) -> u64;
+    pub fn gr_internals_frames(ic: *const gr_internals) -> u64;
+    pub fn gr_internals_values_batch(ic: *mut gr_internals, first_slot: u32, n_frames: u32, out: *mut c_float, status_out: *mut c_int) -> c_int;
+    pub fn gr_internals_values_batch_device(ic: *mut gr_internals, first_slot: u32, n_frames: u32, out_dev: *mut c_float, ld: u64, status_out: *mut c_int) -> c_int;
+    pub fn gr_internals_accumulate_batch(ic: *mut gr_internals, first_slot: u32, n_frames: u32, status_out: *mut c_int) -> c_int;
+    pub fn gr_internals_clear(ic: *mut gr_internals) -> c_int;
+    pub fn gr_internals_read(ic: *mut gr_internals, mean: *mut f64, var: *mut f64) -> c_int;
+    pub fn gr_internals_read_raw(ic: *mut gr_internals, origin: *mut c_float, sum: *mut f64, sumsq: *mut f64, n: *mut u64) -> c_int;
+    pub fn gr_internals_merge(dst: *mut gr_internals, src: *mut gr_internals) -> c_int;
+    pub fn gr_internals_set_launch(ic: *mut gr_internals, tuple_ranges: u32, frame_chunk: u32) -> c_int;
+    pub fn gr_internals_stat(ic: *const gr_internals, key: c_int, value: *mut u64) -> c_int;
     pub fn gr_ctx_set_tuning(ctx: *mut gr_ctx, key: c_int, value: i64) -> c_int;   // GR_TUNE_* (include/groan_hip.h)
     pub fn gr_host_alloc(bytes: usize) -> *mut c_void;                              // pinned memory: asynchronous gr_frame_upload
     pub fn gr_host_free(p: *mut c_void);
