@@ -20,6 +20,7 @@ from .fluct import Fluctuations
 from .covar import Covariance
 from .msd import MSD
 from .internals import Internals, angles_from_bonds, dihedrals_from_bonds
+from .vcorr import VectorCorrelation
 from .xtc import XtcError, XtcFile, XtcWriter
 from .trr import TrrFile, TrrWriter
 from .textio import ParseGroError, ParseNdxError, Structure, read_ndx_groups, system_from_gro, system_read_ndx
@@ -30,6 +31,6 @@ from .parallel import AbortedByOtherRank, Comm, ParallelTrajData, Pool, gather_p
 __all__ = [
     "AtomContainer", "AtomError", "AtomIterator", "DeviceError", "Dimension", "GroanError", "GroupError", "RMSDError", "RMSDPlan",
     "SimBoxError", "System", "pinned_array", "pinned_free", "FrameAnalyze", "FrameConvert", "FrameConvertAnalyze", "RMSDConverterAnalyzer",
-    "TrajAnalyzer", "TrajAnalysisError", "HBOND_DTYPE", "HBondAnalysis", "HBondChain", "HBondError", "GridMap", "GridMapError", "TileGeometry", "Segments", "Region", "Contacts", "RMSDPanel", "rmsd_matrix", "Fluctuations", "Covariance", "MSD", "Internals", "angles_from_bonds", "dihedrals_from_bonds", "TrajConverter", "TrajConverterAnalyzer", "TrajReader",
+    "TrajAnalyzer", "TrajAnalysisError", "HBOND_DTYPE", "HBondAnalysis", "HBondChain", "HBondError", "GridMap", "GridMapError", "TileGeometry", "Segments", "Region", "Contacts", "RMSDPanel", "rmsd_matrix", "Fluctuations", "Covariance", "MSD", "Internals", "angles_from_bonds", "dihedrals_from_bonds", "VectorCorrelation", "TrajConverter", "TrajConverterAnalyzer", "TrajReader",
     "XtcError", "XtcFile", "XtcWriter", "ParseGroError", "ParseNdxError", "Structure", "read_ndx_groups", "system_from_gro", "system_read_ndx", "Cylinder", "Rectangular", "Shape", "Sphere", "TriangularPrism", "AbortedByOtherRank", "Comm", "Pool", "ParallelTrajData", "gather_per_frame", "interleave", "shard_frames", "traj_iter_map_reduce",
 ]

@@ -41,6 +41,10 @@ IC_DISTANCE, IC_ANGLE, IC_DIHEDRAL, IC_AXIS = 1, 2, 3, 4
 IC_PBC = 1
 IC_MAX_WS_BYTES = 64 << 20
 IC_STAT_LAUNCHES, IC_STAT_LAST_RANGE_GROUPS, IC_STAT_LAST_FRAME_GROUPS, IC_STAT_LAST_CHECK_GROUPS, IC_STAT_ARITY, IC_STAT_UNIQUE_ATOMS, IC_STAT_AHEAD = 1, 2, 3, 4, 5, 6, 7
+VCORR_PBC, VCORR_UNIT, VCORR_P1, VCORR_P2 = 1, 2, 4, 8
+VCORR_MAX_EACH_BYTES = 1 << 30
+VCORR_STAT_LAUNCHES, VCORR_STAT_N_PAD, VCORR_STAT_LAGS, VCORR_STAT_LAST_WALK_GROUPS, VCORR_STAT_LAST_GRAM_GROUPS = 1, 2, 3, 4, 5
+VCORR_STAT_LAST_EACH_GROUPS, VCORR_STAT_LAST_BLOCKS, VCORR_STAT_COUNTED = 6, 7, 8
 CT_MAX_BINS = 4096
 MAX_SHAPES = 8
 
@@ -257,6 +261,19 @@ SIGNATURES = {
     "gr_internals_merge": (C.c_int, [C.c_void_p, C.c_void_p]),
     "gr_internals_set_launch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
     "gr_internals_stat": (C.c_int, [C.c_void_p, C.c_int, c_u64p]),
+    "gr_vcorr_create": (C.c_void_p, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, c_i32p]),
+    "gr_vcorr_destroy": (None, [C.c_void_p]),
+    "gr_vcorr_count": (C.c_uint64, [C.c_void_p]),
+    "gr_vcorr_frames": (C.c_uint64, [C.c_void_p]),
+    "gr_vcorr_capacity": (C.c_uint64, [C.c_void_p]),
+    "gr_vcorr_append_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "gr_vcorr_clear": (C.c_int, [C.c_void_p]),
+    "gr_vcorr_compute": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "gr_vcorr_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gr_vcorr_compute_each": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "gr_vcorr_read_vectors": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "gr_vcorr_set_launch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "gr_vcorr_stat": (C.c_int, [C.c_void_p, C.c_int, c_u64p]),
     "gr_group_center_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "gr_group_translate_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_void_p, C.c_void_p]),
     "gr_group_wrap_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_void_p]),

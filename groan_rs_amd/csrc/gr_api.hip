@@ -3738,3 +3738,4 @@ int gr_synth_uniform(gr_ctx *c, uint32_t slot, const float *box9, uint64_t seed)
 #include "gr_covar.h"    // Covariance: positional covariance matrix and DCCM accumulated over batches of resident frames (f64 MFMA rank-K update): kernels, object and C ABI
 #include "gr_msd.h"      // MSD: nojump unwrapping and the windowed mean-squared displacement over resident frames (f64 MFMA Gram product): kernels, object and C ABI
 #include "gr_internals.h" // Internals: distance, angle, dihedral and axis-cosine series of atom tuples over resident frames, and their running statistics: kernel, object and C ABI
+#include "gr_vcorr.h"    // VectorCorrelation: P1/P2 reorientation autocorrelation of bond vectors over resident frames (f64 MFMA Gram product, per-vector VALU chains): kernels, object and C ABI

@@ -48,6 +48,7 @@ typedef struct gr_fluct gr_fluct;
 typedef struct gr_covar gr_covar;
 typedef struct gr_msd gr_msd;
 typedef struct gr_internals gr_internals;
+typedef struct gr_vcorr gr_vcorr;
 typedef struct gr_xtc gr_xtc;
 
 /* status codes; 1..7 map onto the reference's error enums (src/errors.rs) */
@@ -1103,6 +1104,79 @@ int gr_internals_read_raw(gr_internals *ic, float *origin /* [T] */, double *sum
 int gr_internals_merge(gr_internals *dst, gr_internals *src);
 int gr_internals_set_launch(gr_internals *ic, uint32_t tuple_ranges, uint32_t frame_chunk);   /* test hook, 0: default; no result depends on it */
 int gr_internals_stat(const gr_internals *ic, int key, uint64_t *value);
+
+/* ---------------------------------------------------------------- VectorCorrelation: P1/P2 reorientation curves over resident frames
+ * The rotational counterpart of MSD (gmx rotacf): C1(tau) = <u(t) . u(t + tau)> and C2(tau) = <P2(u(t) . u(t + tau))>, P2(x) =
+ * (3 x^2 - 1) / 2, of a fixed list of V bond vectors (i, j) -- water reorientation, lipid dynamics, NMR relaxation and the Lipari-Szabo
+ * S^2 of every N-H bond; the reference has no function for it.  The object keeps up to two PANELS (f32, component-major, V padded with
+ * zeros to n_pad, a multiple of 64) that outlive the slots: X1[capacity][3][n_pad] holds u, X2[capacity][6][n_pad] holds u_x u_x,
+ * u_y u_y, u_z u_z, SQRT2_F (u_x u_y), SQRT2_F (u_x u_z), SQRT2_F (u_y u_z) with SQRT2_F = (float)M_SQRT2 -- for unit vectors
+ * (u . u')^2 = sum_ab (u_a u_b)(u'_a u'_b), so C2 is a Gram product like C1.  With them ok[t].
+ * THE RULE, per good frame and vector, every product and sum rounded on its own, no contraction:
+ *   d = x_j - x_i          ONE f32 subtraction per component; with GR_VCORR_PBC followed by the library's minimum image (triclinic
+ *                          boxes included) with the frame's own box
+ *   with GR_VCORR_UNIT:    len = sqrtf((d_x d_x + d_y d_y) + d_z d_z), correctly rounded; inv = 1.0f / len; u_c = d_c * inv.
+ *                          u = 0 WHEN len = 0: such a vector adds nothing to a sum but STILL COUNTS IN THE DENOMINATOR
+ *   without UNIT:          u = d
+ * ORDER OF THE SUMS.  A lane owns its vector for a launch and takes the frames in ascending order: the panels are a function of the
+ * SEQUENCE of appended frames alone -- not of calls, 1024-frame segments or grids.  gr_vcorr_compute forms S[tau] = sum_t sum_k
+ * X_t . X_(t + tau) over valid pairs as a banded Gram product G = X X^T on the f64 matrix cores (f32 operands widened: exact products,
+ * f64 sums) over the 64 x 64 blocks of frame pairs on and above the diagonal that touch the band; an entry is one chain of one wave over
+ * the K = 3 n_pad (6 n_pad) values of its rows; the diagonal t = t' is a valid pair (lag 0).  The entries of one diagonal of a block are
+ * added in ascending row order, the blocks' partial sums of a lag in ascending block-row order; no atomic decides a sum.  So S[tau] is a
+ * function of the panel alone, the same bits for every max_lag >= tau, grid and context.  gr_vcorr_compute_each closes every
+ * (vector, lag) as ONE sequential f64 chain: frames ascending, within a frame the components in panel order, each term
+ * fma((double)a, (double)b, s).
+ * NOT promised: the bits of S on another device generation or for another n_pad (the four values one matrix instruction adds are
+ * added in an order the hardware does not document); C1[0] = C2[0] = 1 exactly (a stored unit vector has |u|^2 = 1 within f32
+ * rounding).  Out of scope: cross-correlation between two lists, an FFT closing, a merge of objects (time order makes shards
+ * meaningless), S^2 fits and the plateau, normals of three atoms, velocities.
+ *   gr_vcorr_create        atoms: [V][2] row-major, copied.  flags: at least one of GR_VCORR_P1 | GR_VCORR_P2 (the panels to keep),
+ *                          optionally GR_VCORR_PBC, GR_VCORR_UNIT; P2 without UNIT, anything else, V = 0, capacity 0, i == j
+ *                          (gr_last_error_index = the pair), or kept panels above GR_MSD_MAX_PANEL_BYTES: GR_E_INVALID_ARG.  An atom
+ *                          index >= n_atoms: GR_E_OUT_OF_RANGE (gr_last_error_index = the index).  GR_E_HIP when the allocation fails.
+ *   gr_vcorr_append_batch  appends the n_frames slots from first_slot as time indices frames() .. frames() + n_frames - 1.  Per frame:
+ *                          with PBC the box checks come first; a frame in which an atom named by any pair has no position fails with
+ *                          GR_E_NO_POSITION (gr_last_error_index = the lowest such atom).  A FAILED FRAME STILL TAKES A TIME INDEX: its
+ *                          rows are zeros, its ok 0, it enters no pair.  Batch rules: status_out[f] is each frame's status, the return
+ *                          value, message and index are the first failed frame's, a hard error writes nothing.  Beyond the capacity:
+ *                          GR_E_INVALID_ARG, nothing is changed.  The slots may be overwritten as soon as the call returns.
+ *   gr_vcorr_compute       the band up to max_lag (a max_lag beyond frames() - 1 is CLAMPED to it); no frame appended: GR_E_INVALID_ARG
+ *   gr_vcorr_read          closed in f64 on the host: c1[tau] = S1 / (pairs[tau] * V), c2[tau] = 1.5 S2 / (pairs[tau] * V) - 0.5, NaN
+ *                          where pairs[tau] == 0; pairs[tau] counts the t with ok[t] and ok[t + tau].  GR_VCORR_STAT_LAGS values each;
+ *                          each may be NULL; a curve whose panel is not kept, a read before gr_vcorr_compute or after an append or
+ *                          clear behind it: GR_E_INVALID_ARG
+ *   gr_vcorr_compute_each  c1_out, c2_out: [V][lags] (host, f64), the curve of every vector: s / pairs[tau] and 1.5 s / pairs[tau] -
+ *                          0.5.  Each may be NULL, not both; a curve whose panel is not kept, or V x lags x 8 B above
+ *                          GR_VCORR_MAX_EACH_BYTES: GR_E_INVALID_ARG
+ *   gr_vcorr_read_vectors  out[nt][V][3] (f32): rows t0 .. t0 + nt - 1 of the rank-1 panel in the caller's order (needs GR_VCORR_P1)
+ *   gr_vcorr_count         V;  gr_vcorr_frames: time indices taken (failed frames included);  gr_vcorr_capacity
+ *   gr_vcorr_clear         forgets every frame
+ *   gr_vcorr_set_launch    test hook: the ranges of the walk, a cap on the grid of the product and on the grid of compute_each (0: the
+ *                          default).  No result depends on it.
+ *   gr_vcorr_stat          GR_VCORR_STAT_*: launches so far, n_pad, the lags of the last compute, the grids of the last walk, product
+ *                          and compute_each, the blocks of the last compute, the counted frames
+ * The object keeps a pointer to its context: destroy it first. */
+#define GR_VCORR_PBC 1u
+#define GR_VCORR_UNIT 2u
+#define GR_VCORR_P1 4u
+#define GR_VCORR_P2 8u
+#define GR_VCORR_MAX_EACH_BYTES 1073741824u      /* 1 GiB per curve of gr_vcorr_compute_each at most */
+enum { GR_VCORR_STAT_LAUNCHES = 1, GR_VCORR_STAT_N_PAD = 2, GR_VCORR_STAT_LAGS = 3, GR_VCORR_STAT_LAST_WALK_GROUPS = 4, GR_VCORR_STAT_LAST_GRAM_GROUPS = 5,
+       GR_VCORR_STAT_LAST_EACH_GROUPS = 6, GR_VCORR_STAT_LAST_BLOCKS = 7, GR_VCORR_STAT_COUNTED = 8 };
+gr_vcorr *gr_vcorr_create(gr_ctx *ctx, const uint64_t *atoms /* [V][2], row-major */, uint64_t n_vectors, uint32_t capacity_frames, uint32_t flags, int *status);
+void gr_vcorr_destroy(gr_vcorr *vc);
+uint64_t gr_vcorr_count(const gr_vcorr *vc);
+uint64_t gr_vcorr_frames(const gr_vcorr *vc);
+uint64_t gr_vcorr_capacity(const gr_vcorr *vc);
+int gr_vcorr_append_batch(gr_vcorr *vc, uint32_t first_slot, uint32_t n_frames, int *status_out /* [n_frames] or NULL */);
+int gr_vcorr_clear(gr_vcorr *vc);
+int gr_vcorr_compute(gr_vcorr *vc, uint32_t max_lag);
+int gr_vcorr_read(gr_vcorr *vc, double *c1 /* [lags] */, double *c2 /* [lags] */, uint64_t *pairs /* [lags] */);
+int gr_vcorr_compute_each(gr_vcorr *vc, uint32_t max_lag, double *c1_out /* [V][lags] */, double *c2_out /* [V][lags] */);
+int gr_vcorr_read_vectors(gr_vcorr *vc, uint32_t t0, uint32_t nt, float *out /* [nt][V][3] */);
+int gr_vcorr_set_launch(gr_vcorr *vc, uint32_t walk_groups, uint32_t gram_groups, uint32_t each_groups);   /* test hook, 0: default; no result depends on it */
+int gr_vcorr_stat(const gr_vcorr *vc, int key, uint64_t *value);
 
 /* ---------------------------------------------------------------- xtc reader (host side)
  * The stage in front of the path: XtcReader (src/io/xtc_io/mod.rs, molly_xtc.rs:96-308, xdrfile_xtc.rs:42-104).

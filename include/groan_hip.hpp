@@ -1226,6 +1226,83 @@ class Msd {
     gr_msd *f_ = nullptr;
 };
 
+// ---- VectorCorrelation: the P1 / P2 reorientation autocorrelation functions of a fixed list of bond vectors (i, j) over the frames
+// handed to append() (gmx rotacf; the rotational counterpart of Msd): correlate() closes the band of lags over all vectors on the f64
+// matrix cores, correlate_each() gives the curve of every vector.  groan_hip.h has the rule, the order of the sums and what is not promised.
+class VectorCorrelation {
+  public:
+    struct Curves { std::vector<double> c1, c2; std::vector<uint64_t> pairs; };     // [lags] each; c1 / c2 empty for a rank that is not kept, NaN where pairs is 0
+    struct Each { std::vector<double> c1, c2; size_t lags = 0; };                   // [V][lags] each; empty for a rank that is not kept
+
+    // pairs: [V][2] row-major
+    VectorCorrelation(System &system, const std::vector<uint64_t> &pairs, uint32_t capacity_frames,
+                      uint32_t flags = GR_VCORR_UNIT | GR_VCORR_P1 | GR_VCORR_P2) : ctx_(system.raw()), flags_(flags) {
+        int st = 0;
+        f_ = gr_vcorr_create(ctx_, pairs.data(), pairs.size() / 2, capacity_frames, flags, &st);
+        if (!f_) raise(st);
+    }
+    ~VectorCorrelation() { if (f_) gr_vcorr_destroy(f_); }
+    VectorCorrelation(const VectorCorrelation &) = delete;
+    VectorCorrelation &operator=(const VectorCorrelation &) = delete;
+    VectorCorrelation(VectorCorrelation &&o) noexcept : ctx_(o.ctx_), f_(o.f_), flags_(o.flags_) { o.f_ = nullptr; }
+
+    uint64_t count() const { return gr_vcorr_count(f_); }
+    uint64_t frames() const { return gr_vcorr_frames(f_); }
+    uint64_t capacity() const { return gr_vcorr_capacity(f_); }
+    // appends n_frames slots from first_slot; a failed frame takes a time index and enters no pair; throws the first failure unless
+    // `status` is given.  A refused call (beyond the capacity, slots out of range) always throws
+    void append(uint32_t first_slot, uint32_t n_frames, std::vector<int> *status = nullptr) {
+        std::vector<int> st(n_frames);
+        const int r = gr_vcorr_append_batch(f_, first_slot, n_frames, st.data());
+        detail::batch_status(r, st, status, [this](int e) { raise(e); });
+    }
+    void clear() { check(gr_vcorr_clear(f_)); }
+    // the curves over all vectors for lags 0 .. max_lag (clamped to frames() - 1)
+    Curves correlate(uint32_t max_lag = 0xFFFFFFFFu) {
+        check(gr_vcorr_compute(f_, max_lag));
+        Curves c;
+        const size_t lags = (size_t)stat(GR_VCORR_STAT_LAGS);
+        if (flags_ & GR_VCORR_P1) c.c1.resize(lags);
+        if (flags_ & GR_VCORR_P2) c.c2.resize(lags);
+        c.pairs.resize(lags);
+        check(gr_vcorr_read(f_, c.c1.empty() ? nullptr : c.c1.data(), c.c2.empty() ? nullptr : c.c2.data(), c.pairs.data()));
+        return c;
+    }
+    // the curves of every vector
+    Each correlate_each(uint32_t max_lag = 0xFFFFFFFFu) {
+        Each e;
+        const uint64_t n = frames();
+        e.lags = (size_t)std::min<uint64_t>(max_lag, n ? n - 1 : 0) + 1;
+        if (flags_ & GR_VCORR_P1) e.c1.resize((size_t)count() * e.lags);
+        if (flags_ & GR_VCORR_P2) e.c2.resize((size_t)count() * e.lags);
+        check(gr_vcorr_compute_each(f_, max_lag, e.c1.empty() ? nullptr : e.c1.data(), e.c2.empty() ? nullptr : e.c2.data()));
+        return e;
+    }
+    // [nt][V][3]: rows t0 .. t0 + nt - 1 of the rank-1 panel in the caller's order
+    std::vector<float> vectors(uint32_t t0, uint32_t nt) {
+        std::vector<float> d((size_t)nt * 3 * count());
+        check(gr_vcorr_read_vectors(f_, t0, nt, d.data()));
+        return d;
+    }
+    void set_launch(uint32_t walk_groups, uint32_t gram_groups, uint32_t each_groups) { gr_vcorr_set_launch(f_, walk_groups, gram_groups, each_groups); }
+    uint64_t stat(int key) const { uint64_t v = 0; if (gr_vcorr_stat(f_, key, &v) != GR_OK) throw std::invalid_argument("VectorCorrelation::stat | unknown key"); return v; }
+    gr_vcorr *raw_handle() const { return f_; }
+
+  private:
+    void check(int st) const { if (st != GR_OK) raise(st); }
+    [[noreturn]] void raise(int st) const {
+        switch (st) {
+        case GR_E_OUT_OF_RANGE: throw Error("AtomError", "OutOfRange", st, gr_last_error_index(ctx_));
+        case GR_E_NO_POSITION: throw Error("AtomError", "InvalidPosition", st, gr_last_error_index(ctx_));
+        case GR_E_NO_BOX: throw Error("SimBoxError", "DoesNotExist", st);
+        default: throw Error("DeviceError", std::string(gr_status_string(st)) + ": " + gr_last_error(ctx_), st);
+        }
+    }
+    gr_ctx *ctx_ = nullptr;
+    gr_vcorr *f_ = nullptr;
+    uint32_t flags_ = 0;
+};
+
 // ---- Internals: the distance, angle, dihedral or axis cosine of a fixed list of atom tuples in every frame of a block of resident
 // frames (values), or their running mean and variance over any number of calls (accumulate); the reference has Vector3D::angle and
 // distance only.  Angles in radians, the dihedral's sign is IUPAC's (groan_hip.h has the definitions).  The sums are added frame after

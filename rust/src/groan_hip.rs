@@ -79,6 +79,19 @@ pub const GR_MSD_STAT_LAST_BLOCKS: c_int = 6;
 pub const GR_MSD_STAT_LAGS: c_int = 7;
 pub const GR_MSD_STAT_N_PAD: c_int = 8;
 pub const GR_MSD_STAT_COUNTED: c_int = 9;
+pub const GR_VCORR_PBC: u32 = 1;
+pub const GR_VCORR_UNIT: u32 = 2;
+pub const GR_VCORR_P1: u32 = 4;
+pub const GR_VCORR_P2: u32 = 8;
+pub const GR_VCORR_MAX_EACH_BYTES: u64 = 1073741824;
+pub const GR_VCORR_STAT_LAUNCHES: c_int = 1;
+pub const GR_VCORR_STAT_N_PAD: c_int = 2;
+pub const GR_VCORR_STAT_LAGS: c_int = 3;
+pub const GR_VCORR_STAT_LAST_WALK_GROUPS: c_int = 4;
+pub const GR_VCORR_STAT_LAST_GRAM_GROUPS: c_int = 5;
+pub const GR_VCORR_STAT_LAST_EACH_GROUPS: c_int = 6;
+pub const GR_VCORR_STAT_LAST_BLOCKS: c_int = 7;
+pub const GR_VCORR_STAT_COUNTED: c_int = 8;
 
 #[repr(C)] pub struct gr_hbond_plan { _private: [u8; 0] }
 #[repr(C)] pub struct gr_gridmap { _private: [u8; 0] }
@@ -90,6 +103,7 @@ pub const GR_MSD_STAT_COUNTED: c_int = 9;
 #[repr(C)] pub struct gr_covar { _private: [u8; 0] }
 #[repr(C)] pub struct gr_msd { _private: [u8; 0] }
 #[repr(C)] pub struct gr_internals { _private: [u8; 0] }
+#[repr(C)] pub struct gr_vcorr { _private: [u8; 0] }
 #[repr(C)] pub struct gr_pool { _private: [u8; 0] }
 #[repr(C)] pub struct gr_comm { _private: [u8; 0] }
 /// `body(ctx, worker, frame, user, result)` of gr_pool_map: non-zero return = the frame's error (the first one wins)
@@ -302,6 +316,20 @@ extern "C" {
     pub fn gr_internals_merge(dst: *mut gr_internals, src: *mut gr_internals) -> c_int;
     pub fn gr_internals_set_launch(ic: *mut gr_internals, tuple_ranges: u32, frame_chunk: u32) -> c_int;
     pub fn gr_internals_stat(ic: *const gr_internals, key: c_int, value: *mut u64) -> c_int;
+    // VectorCorrelation: P1 / P2 reorientation autocorrelation of V bond vectors over resident frames (atoms: [V][2]; flags: GR_VCORR_PBC | _UNIT | _P1 | _P2; status_out, c1, c2, pairs and one of c1_out / c2_out may be null)
+    pub fn gr_vcorr_create(ctx: *mut gr_ctx, atoms: *const u64, n_vectors: u64, capacity_frames: u32, flags: u32, status: *mut c_int) -> *mut gr_vcorr;
+    pub fn gr_vcorr_destroy(vc: *mut gr_vcorr);
+    pub fn gr_vcorr_count(vc: *const gr_vcorr) -> u64;
+    pub fn gr_vcorr_frames(vc: *const gr_vcorr) -> u64;
+    pub fn gr_vcorr_capacity(vc: *const gr_vcorr) -> u64;
+    pub fn gr_vcorr_append_batch(vc: *mut gr_vcorr, first_slot: u32, n_frames: u32, status_out: *mut c_int) -> c_int;
+    pub fn gr_vcorr_clear(vc: *mut gr_vcorr) -> c_int;
+    pub fn gr_vcorr_compute(vc: *mut gr_vcorr, max_lag: u32) -> c_int;
+    pub fn gr_vcorr_read(vc: *mut gr_vcorr, c1: *mut f64, c2: *mut f64, pairs: *mut u64) -> c_int;
+    pub fn gr_vcorr_compute_each(vc: *mut gr_vcorr, max_lag: u32, c1_out: *mut f64, c2_out: *mut f64) -> c_int;
+    pub fn gr_vcorr_read_vectors(vc: *mut gr_vcorr, t0: u32, nt: u32, out: *mut c_float) -> c_int;
+    pub fn gr_vcorr_set_launch(vc: *mut gr_vcorr, walk_groups: u32, gram_groups: u32, each_groups: u32) -> c_int;
+    pub fn gr_vcorr_stat(vc: *const gr_vcorr, key: c_int, value: *mut u64) -> c_int;
     pub fn gr_ctx_set_tuning(ctx: *mut gr_ctx, key: c_int, value: i64) -> c_int;   // GR_TUNE_* (include/groan_hip.h)
     pub fn gr_host_alloc(bytes: usize) -> *mut c_void;                              // pinned memory: asynchronous gr_frame_upload
     pub fn gr_host_free(p: *mut c_void);
