@@ -3733,6 +3733,8 @@ int gr_synth_uniform(gr_ctx *c, uint32_t slot, const float *box9, uint64_t seed)
 #include "gr_segments.h" // Segments: per-residue / per-molecule centres of resident frames: partition, kernel and C ABI
 #include "gr_region.h"   // Region: geometry selections over a block of resident frames: kernels, object and C ABI
 #include "gr_contacts.h" // Contacts: cut-off pair search over a block of resident frames: kernels, object and C ABI
+#include "gr_series.h"   // what the objects over batches of resident frames share: snapshot, tuple table, the round of verdicts (k_fl_check), destroy
+#include "gr_band.h"     // the band product of MSD and VectorCorrelation: geometry (host and device), k_band_gram, k_band_lags, the launch
 #include "gr_rmsd_panel.h" // RMSDPanel: packed centred frames and their all-pairs RMSD matrix (f64 MFMA product): kernels, object and C ABI
 #include "gr_fluct.h"    // Fluctuations: mean structure and per-atom RMSF accumulated over batches of resident frames: kernels, object and C ABI
 #include "gr_covar.h"    // Covariance: positional covariance matrix and DCCM accumulated over batches of resident frames (f64 MFMA rank-K update): kernels, object and C ABI

@@ -6,7 +6,7 @@
 //   Q  (f64) [R][R]   sum over the counted frames of e e^T, e = (d_0 .. d_{D-1}, 1), d = x - o as ONE f32 subtraction, then widened; R = D + 1.
 //                     Row / column D of Q is s = sum d, Q[D][D] the number of counted frames: s and n come out of the same product.
 // and the host closes them in f64 (cv_close).  Only the upper BLOCK triangle of Q is stored, in blocks of GR_CV_BLOCK x GR_CV_BLOCK.
-//   k_fl_check     (gr_fluct.h) the first atom of the group without position, per frame
+//   k_fl_check     (gr_series.h) the first atom of the group without position, per frame
 //   k_cv_origin    the first clean frame of an empty object sets o
 //   k_cv_pack      a segment of up to 1024 frames -> the dimension-major panel P[R_pad][K_pad] (f32, frames contiguous, K_pad a multiple of
 //                  GR_CV_TRIP): P[r][f] = x_f[r] - o[r], row D = 1.0.  Columns of failed frames and of padding, rows of padding: ZEROS --
@@ -38,15 +38,12 @@
 struct gr_covar {
     gr_ctx *c = nullptr;
     std::string group;
-    std::vector<uint32_t> atoms;          // the snapshot, group order (ascending)
+    GrSnapshot snap;                      // the group's atoms at create
+    GrVerdicts verdicts;
     std::vector<float> masses;            // of the snapshot's atoms at create (the closing step's only)
-    uint32_t n_atoms = 0, units = 0;
+    uint32_t n_atoms = 0;
     uint32_t D = 0, R = 0, rpad = 0, nblk = 0;        // dimensions, rows of the product (D + 1), ... rounded up to the block, block rows
     uint64_t ntri = 0;                    // blocks stored: nblk (nblk + 1) / 2
-    int form = 0;                         // as Fluctuations': how k_fl_check walks the snapshot
-    GrSel sel = {};
-    grbuf::Dev<uint32_t> atoms_dev, mask_dev, verdict_dev;
-    grbuf::Pinned<uint32_t> verdict_host;
     grbuf::Dev<float> o, panel;           // [rpad], [rpad][GR_MAX_BATCH]
     grbuf::Dev<double> Q;                 // [ntri][GR_CV_BLOCK_LEN]
     uint64_t n = 0;                       // counted frames
@@ -229,32 +226,28 @@ int cv_accumulate(gr_covar *f, uint32_t first_slot, uint32_t n_frames, int *stat
     gr_ctx *c = f->c;
     int st = slot_check(c, first_slot, n_frames); if (st) return st;
     (void)hipSetDevice(c->device);
-    const GrSel sel = f->sel;
-    uint32_t *vh = f->verdict_host.get(), *vd = f->verdict_dev.get();
+    GrVerdicts &V = f->verdicts;
+    const uint32_t *vd = V.dev.get(), *atoms = f->snap.atoms_dev.get();
     grb::FirstError<gr_ctx> fe;
     for (const auto [b0, nb, s0] : grb::Segments{ first_slot, n_frames }) {
         const grb::Prechecks pre(c, { b0, nb, s0 }, box_checks(c, false));
-        for (uint32_t k = 0; k < nb; ++k) vh[k] = pre.ok(k) ? GR_NOIDX : GR_FL_SKIP;
         if (pre.any_ok) {
             SlotUse use(c, s0, nb);
-            HIPCHK(c, hipMemcpyAsync(vd, vh, nb * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-            // launch geometry: one workgroup per stored block of Q, 256 units per workgroup of the check; gr_covar_set_launch caps both grids
+            st = V.begin(c, pre, nb); if (st) return st;
+            // launch geometry: one workgroup per stored block of Q; gr_covar_set_launch caps both grids
             const uint32_t kpad = (nb + GR_CV_TRIP - 1u) & ~(GR_CV_TRIP - 1u);
             uint32_t product = (uint32_t)f->ntri;
             if (f->product_groups && f->product_groups < product) product = f->product_groups;
-            uint32_t check = std::min<uint32_t>((f->units + 255u) / 256u, GR_FL_CHECK_WGS);
-            if (f->check_groups && f->check_groups < check) check = f->check_groups;
-            k_fl_check<<<dim3(check, nb), dim3(256), 0, c->stream>>>(c->frames, c->frame_stride, s0, sel, f->form, vd);
-            if (f->n == 0) k_cv_origin<<<dim3((f->D + 255u) / 256u), dim3(256), 0, c->stream>>>(c->frames, c->frame_stride, s0, nb, f->atoms_dev.get(), f->D, vd, f->o.get());
-            k_cv_pack<<<dim3(f->rpad / 64u, (kpad + 63u) / 64u), dim3(256), 0, c->stream>>>(c->frames, c->frame_stride, s0, nb, kpad, f->atoms_dev.get(), f->D, vd, f->o.get(), f->panel.get());
+            const uint32_t check = V.check(c, f->snap, s0, nb, f->check_groups);
+            if (f->n == 0) k_cv_origin<<<dim3((f->D + 255u) / 256u), dim3(256), 0, c->stream>>>(c->frames, c->frame_stride, s0, nb, atoms, f->D, vd, f->o.get());
+            k_cv_pack<<<dim3(f->rpad / 64u, (kpad + 63u) / 64u), dim3(256), 0, c->stream>>>(c->frames, c->frame_stride, s0, nb, kpad, atoms, f->D, vd, f->o.get(), f->panel.get());
             k_cv_product<<<dim3(product), dim3(256), 0, c->stream>>>(f->panel.get(), kpad, f->nblk, (uint32_t)f->ntri, f->Q.get());
             HIPCHK(c, hipGetLastError());
             ++f->launches; f->last_product = product; f->last_check = check;
-            HIPCHK(c, hipMemcpyAsync(vh, vd, nb * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
+            st = V.end(c, nb); if (st) return st;
         }
         for (uint32_t k = 0; k < nb; ++k) {
-            const int s = grb::close_frame(c, fe, pre, k, status_out, [&] { return vh[k] != GR_NOIDX ? fail(c, GR_E_NO_POSITION, "atom has no position", vh[k]) : (int)GR_OK; });
+            const int s = grb::close_frame(c, fe, pre, k, status_out, [&] { return V.judge(c, k); });
             if (s == GR_OK) ++f->n;
         }
     }
@@ -272,50 +265,31 @@ gr_covar *gr_covar_create(gr_ctx *c, const char *group, int *status) try {
     const Group *g = need_group(c, group, *status, true); if (!g) return nullptr;
     std::unique_ptr<gr_covar> f(new gr_covar());
     f->c = c; f->group = group;
-    f->atoms = hb_group_atoms(*g);
-    if (f->atoms.size() > GR_CV_MAX_ATOMS) {
+    std::vector<uint32_t> atoms = hb_group_atoms(*g);
+    if (atoms.size() > GR_CV_MAX_ATOMS) {
         *status = fail(c, GR_E_INVALID_ARG, "covariance: the group has more than GR_CV_MAX_ATOMS = " + std::to_string(GR_CV_MAX_ATOMS) + " atoms");
         return nullptr;
     }
-    f->n_atoms = (uint32_t)f->atoms.size();
-    for (uint32_t a : f->atoms) f->masses.push_back(c->masses_host[a]);
+    f->n_atoms = (uint32_t)atoms.size();
+    for (uint32_t a : atoms) f->masses.push_back(c->masses_host[a]);
     f->D = 3u * f->n_atoms; f->R = f->D + 1u;
     f->rpad = (f->R + GR_CV_BLOCK - 1u) & ~(GR_CV_BLOCK - 1u);
     f->nblk = f->rpad / GR_CV_BLOCK;
     f->ntri = (uint64_t)f->nblk * (f->nblk + 1u) / 2u;
-    const uint32_t a0 = f->atoms.front(), span = f->atoms.back() - a0 + 1u;
-    f->form = span == f->n_atoms ? 0 : (2ull * f->n_atoms >= span ? 2 : 1);
-    f->units = f->form == 1 ? f->n_atoms : ((a0 + span - 1u) >> 2) - (a0 >> 2) + 1u;
     (void)hipSetDevice(c->device);
-    bool ok = f->atoms_dev.reserve(f->n_atoms, grbuf::exact) == hipSuccess && f->o.reserve(f->rpad, grbuf::exact) == hipSuccess &&
-              f->panel.reserve((size_t)f->rpad * GR_MAX_BATCH, grbuf::exact) == hipSuccess && f->Q.reserve(cv_q_len(f.get()), grbuf::exact) == hipSuccess &&
-              f->verdict_dev.reserve(GR_MAX_BATCH, grbuf::exact) == hipSuccess && f->verdict_host.reserve(GR_MAX_BATCH, grbuf::exact) == hipSuccess;
-    ok = ok && hipMemcpy(f->atoms_dev.get(), f->atoms.data(), 4 * (size_t)f->n_atoms, hipMemcpyHostToDevice) == hipSuccess;
-    if (ok && f->form == 2) {
-        std::vector<uint32_t> bits(((size_t)c->n_pad + 31) / 32, 0u);
-        for (uint32_t a : f->atoms) bits[a >> 5] |= 1u << (a & 31u);
-        ok = f->mask_dev.reserve(bits.size(), grbuf::exact) == hipSuccess && hipMemcpy(f->mask_dev.get(), bits.data(), 4 * bits.size(), hipMemcpyHostToDevice) == hipSuccess;
-    }
+    bool ok = f->snap.build(c, std::move(atoms)) && f->verdicts.reserve(0u) && f->o.reserve(f->rpad, grbuf::exact) == hipSuccess &&
+              f->panel.reserve((size_t)f->rpad * GR_MAX_BATCH, grbuf::exact) == hipSuccess && f->Q.reserve(cv_q_len(f.get()), grbuf::exact) == hipSuccess;
     ok = ok && cv_zero(f.get()) == GR_OK && hipStreamSynchronize(c->stream) == hipSuccess;
     if (!ok) {
         (void)hipGetLastError();
         *status = fail(c, GR_E_HIP, "covariance: device allocation failed");
         return nullptr;
     }
-    // the snapshot as a selection of its own: the group may be replaced or removed while the object lives
-    GrSel &s = f->sel;
-    s.n = f->n_atoms; s.contiguous = f->form == 0 ? 1u : 0u; s.start = a0; s.g0 = a0 >> 8; s.idx = f->atoms_dev.get();
-    s.masked = f->form == 2 ? 1u : 0u; s.span = span; s.mask = f->form == 2 ? f->mask_dev.get() : nullptr;
     *status = GR_OK;
     return f.release();
 } catch (...) { if (status) *status = gr_abi_guard(); return nullptr; }
 
-void gr_covar_destroy(gr_covar *f) try {
-    if (!f) return;
-    (void)hipSetDevice(f->c->device);
-    (void)hipStreamSynchronize(f->c->stream);
-    delete f;                                              // (frees the grow-only buffers)
-} catch (...) { }
+void gr_covar_destroy(gr_covar *f) try { gr_object_destroy(f); } catch (...) { }
 
 int gr_covar_accumulate_batch(gr_covar *f, uint32_t first_slot, uint32_t n_frames, int *status_out) try {
     if (!f) return GR_E_INVALID_ARG;

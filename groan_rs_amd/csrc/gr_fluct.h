@@ -9,8 +9,8 @@
 // ORDER OF THE SUMS: a lane owns its atoms for the whole launch and adds the frames in ascending order, one after another; nothing is
 // split over frames, no atomic touches a sum.  So s and q are a function of the SEQUENCE of counted frames alone -- not of how the frames
 // were cut into calls, 1024-frame segments or grids -- and tests/fluct_ref.py restates them bit for bit in three lines of numpy.
-//   k_fl_check        read-only pass over the x rows: the first atom of the group without position, per frame (atomicMin into the frame's
-//                     verdict word).  A frame with such an atom is counted for NO atom.
+//   k_fl_check        (gr_series.h, with the snapshot and the round of verdicts) the first atom of the group without position, per frame.
+//                     A frame with such an atom is counted for NO atom.
 //   k_fl_accumulate   one wave per range of the group's UNITS (4-atom groups of the span for a contiguous or masked group, list entries
 //                     for an index list).  A lane loads the state of its unit, walks the segment's frames with the rows of GR_FL_AHEAD
 //                     frames in flight (buffer loads: a frame beyond the segment is a resource of zero records, a unit beyond the range an
@@ -24,14 +24,12 @@
 // STATE LAYOUT: component-major in pieces of 16 bytes per unit -- float4 [3][units] for o, double2 [6][units] for s and for q (index list:
 // float [3][units], double [3][units]) -- so every state load and store of a wave is one contiguous block.
 #pragma once
-#include "gr_kernels.h"
+#include "gr_series.h"
 
 #if defined(__HIPCC__)
 
 #define GR_FL_AHEAD 8                     /* frames whose rows a lane has in flight */
 #define GR_FL_WG 64u                      /* lanes of a workgroup of k_fl_accumulate: one wave */
-#define GR_FL_SKIP 0xFFFFFFFEu            /* verdict word: the frame failed its host checks, no kernel touches it (GR_NOIDX: every atom has a position) */
-#define GR_FL_CHECK_WGS 4096u             /* k_fl_check's grid along x at most */
 #define GR_FL_MAX_RANGES (1u << 22)       /* k_fl_accumulate's grid at most */
 
 struct GrFlState {
@@ -43,12 +41,9 @@ struct GrFlState {
 struct gr_fluct {
     gr_ctx *c = nullptr;
     std::string group;
-    std::vector<uint32_t> atoms;          // the snapshot, group order (ascending)
-    uint32_t n_atoms = 0, units = 0, upad = 0;
-    int form = 0;                         // 0: a contiguous block, 1: index list, 2: masked span (at least half of the span's atoms are the group's)
-    GrSel sel = {};
-    grbuf::Dev<uint32_t> atoms_dev, mask_dev, verdict_dev;
-    grbuf::Pinned<uint32_t> verdict_host;
+    GrSnapshot snap;                      // the group's atoms at create
+    GrVerdicts verdicts;
+    uint32_t n_atoms = 0, upad = 0;       // ..., the snapshot's units rounded up to the wave
     grbuf::Dev<float> o, mean_dev;        // [C * upad], [n_atoms][3]
     grbuf::Dev<double> s, q;              // [C * upad]
     uint64_t n = 0;                       // counted frames
@@ -63,41 +58,6 @@ namespace {
 
 __device__ __forceinline__ float fl_buf_load_f32_stream(__amdgpu_buffer_rsrc_t r, uint32_t byte_off) {
     return __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, (int)byte_off, 0, 2 /* nt */));
-}
-
-__global__ __launch_bounds__(256) void k_fl_check(const float *__restrict__ frames, size_t stride, uint32_t s0, GrSel sel, int form, uint32_t *verdict) {
-    const uint32_t f = blockIdx.y;
-    if (verdict[f] == GR_FL_SKIP) return;
-    const float *xyz = frames + (size_t)(s0 + f) * stride;
-    const uint32_t step = gridDim.x * 256u;
-    uint32_t bad = GR_NOIDX;
-    if (form == 1) {
-        for (uint32_t k = blockIdx.x * 256u + threadIdx.x; k < sel.n; k += step) {
-            const uint32_t i = sel.idx[k];
-            const float x = xyz[gr_tile_index(i, 0)];
-            if (x != x) bad = min(bad, i);
-        }
-    } else {
-        const float4 *f4 = reinterpret_cast<const float4 *>(xyz);
-        const uint32_t a0 = sel.start, a1 = sel.start + sel.span;
-        for (uint32_t g = (a0 >> 2) + blockIdx.x * 256u + threadIdx.x; g <= (a1 - 1u) >> 2; g += step) {
-            const size_t b = gr_row_index(g, 0);
-            const float4 r0 = f4[b], r1 = f4[b + 64];     // x of the lane's atoms: row 0 .x .y, row 1 .z .w
-            const float x[4] = { r0.x, r0.y, r1.z, r1.w };
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const uint32_t i = 4u * g + (uint32_t)k;
-                const bool in = i >= a0 && i < a1 && (form == 0 || ((sel.mask[i >> 5] >> (i & 31u)) & 1u));
-                if (in && x[k] != x[k]) bad = min(bad, i);
-            }
-        }
-    }
-    // (rare: a wave that has such an atom reduces and reports it, the others do nothing)
-    if (__builtin_amdgcn_ballot_w64(bad != GR_NOIDX) != 0ull) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) bad = min(bad, (uint32_t)__shfl_xor((int)bad, off, 64));
-        if ((threadIdx.x & 63u) == 0u) atomicMin(&verdict[f], bad);
-    }
 }
 
 // frames [s0, s0 + nf) of `frames`, verdict[f] per frame and GR_FL_SKIP in verdict[nf .. nf + 2 * GR_FL_AHEAD); have_origin: the object has counted a frame before this launch
@@ -244,11 +204,11 @@ __global__ __launch_bounds__(256) void k_fl_store_mean(float *__restrict__ xyz, 
 
 // element of component c of the group's k-th atom inside a state array whose pieces hold V values (4: o, 2: s and q; the index list: 1)
 size_t fl_at(const gr_fluct *f, uint32_t k, int c, uint32_t V) {
-    if (f->form == 1) return (size_t)c * f->upad + k;
-    const uint32_t i = f->atoms[k], u = (i >> 2) - (f->atoms[0] >> 2), j = ((i >> 1) & 1u) * 6u + 2u * (uint32_t)c + (i & 1u);
+    if (f->snap.form == 1) return (size_t)c * f->upad + k;
+    const uint32_t i = f->snap.atoms[k], u = (i >> 2) - (f->snap.atoms[0] >> 2), j = ((i >> 1) & 1u) * 6u + 2u * (uint32_t)c + (i & 1u);
     return (size_t)(j / V) * f->upad * V + (size_t)u * V + j % V;
 }
-size_t fl_state_len(const gr_fluct *f) { return (size_t)(f->form == 1 ? 3u : 12u) * f->upad; }
+size_t fl_state_len(const gr_fluct *f) { return (size_t)(f->snap.form == 1 ? 3u : 12u) * f->upad; }
 
 // the state in group order, [n_atoms][3] each
 int fl_get(gr_fluct *f, std::vector<float> &o, std::vector<double> &s, std::vector<double> &q) {
@@ -262,7 +222,7 @@ int fl_get(gr_fluct *f, std::vector<float> &o, std::vector<double> &s, std::vect
     HIPCHK(c, hipMemcpy(qd.data(), f->q.get(), len * sizeof(double), hipMemcpyDeviceToHost));
     const size_t S = f->n_atoms;
     o.resize(3 * S); s.resize(3 * S); q.resize(3 * S);
-    const uint32_t vo = f->form == 1 ? 1u : 4u, vs = f->form == 1 ? 1u : 2u;
+    const uint32_t vo = f->snap.form == 1 ? 1u : 4u, vs = f->snap.form == 1 ? 1u : 2u;
     for (uint32_t k = 0; k < f->n_atoms; ++k)
         for (int a = 0; a < 3; ++a) { o[3 * (size_t)k + a] = od[fl_at(f, k, a, vo)]; s[3 * (size_t)k + a] = sd[fl_at(f, k, a, vs)]; q[3 * (size_t)k + a] = qd[fl_at(f, k, a, vs)]; }
     return GR_OK;
@@ -274,7 +234,7 @@ int fl_put(gr_fluct *f, const std::vector<float> &o, const std::vector<double> &
     (void)hipSetDevice(c->device);
     const size_t len = fl_state_len(f);
     std::vector<float> od(len, 0.0f); std::vector<double> sd(len, 0.0), qd(len, 0.0);
-    const uint32_t vo = f->form == 1 ? 1u : 4u, vs = f->form == 1 ? 1u : 2u;
+    const uint32_t vo = f->snap.form == 1 ? 1u : 4u, vs = f->snap.form == 1 ? 1u : 2u;
     for (uint32_t k = 0; k < f->n_atoms; ++k)
         for (int a = 0; a < 3; ++a) { od[fl_at(f, k, a, vo)] = o[3 * (size_t)k + a]; sd[fl_at(f, k, a, vs)] = s[3 * (size_t)k + a]; qd[fl_at(f, k, a, vs)] = q[3 * (size_t)k + a]; }
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -306,34 +266,29 @@ int fl_accumulate(gr_fluct *f, uint32_t first_slot, uint32_t n_frames, int *stat
     gr_ctx *c = f->c;
     int st = slot_check(c, first_slot, n_frames); if (st) return st;
     (void)hipSetDevice(c->device);
-    const GrSel sel = f->sel;
-    const int form = f->form;
+    const GrSel sel = f->snap.sel;
+    const int form = f->snap.form;
     const uint32_t slot_bytes = (uint32_t)(c->frame_stride * sizeof(float));
     const GrFlState S = { f->o.get(), f->s.get(), f->q.get(), f->upad };
-    uint32_t *vh = f->verdict_host.get(), *vd = f->verdict_dev.get();
+    GrVerdicts &V = f->verdicts;
+    const uint32_t *vd = V.dev.get();
     grb::FirstError<gr_ctx> fe;
     for (const auto [b0, nb, s0] : grb::Segments{ first_slot, n_frames }) {
         const grb::Prechecks pre(c, { b0, nb, s0 }, box_checks(c, false));
-        for (uint32_t k = 0; k < nb; ++k) vh[k] = pre.ok(k) ? GR_NOIDX : GR_FL_SKIP;
-        for (uint32_t k = nb; k < nb + 2u * GR_FL_AHEAD; ++k) vh[k] = GR_FL_SKIP;
         if (pre.any_ok) {
             SlotUse use(c, s0, nb);
-            HIPCHK(c, hipMemcpyAsync(vd, vh, (nb + 2u * GR_FL_AHEAD) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-            // launch geometry: one wave per 64 units, 256 units per workgroup of the check (up to GR_FL_CHECK_WGS that stride); gr_fluct_set_launch replaces the
-            // number of ranges and caps the check's grid
-            const uint32_t wx = std::min<uint32_t>(f->range_groups ? f->range_groups : (f->units + GR_FL_WG - 1u) / GR_FL_WG, GR_FL_MAX_RANGES);
-            uint32_t check = std::min<uint32_t>((f->units + 255u) / 256u, GR_FL_CHECK_WGS);
-            if (f->check_groups && f->check_groups < check) check = f->check_groups;
-            k_fl_check<<<dim3(check, nb), dim3(256), 0, c->stream>>>(c->frames, c->frame_stride, s0, sel, form, vd);
+            st = V.begin(c, pre, nb); if (st) return st;
+            // launch geometry: one wave per 64 units; gr_fluct_set_launch replaces the number of ranges and caps the check's grid
+            const uint32_t wx = std::min<uint32_t>(f->range_groups ? f->range_groups : (f->snap.units + GR_FL_WG - 1u) / GR_FL_WG, GR_FL_MAX_RANGES);
+            const uint32_t check = V.check(c, f->snap, s0, nb, f->check_groups);
             if (form == 1) k_fl_accumulate<true><<<dim3(wx), dim3(GR_FL_WG), 0, c->stream>>>(c->frames, c->frame_stride, slot_bytes, s0, nb, sel, form, vd, S, f->n ? 1u : 0u);
             else k_fl_accumulate<false><<<dim3(wx), dim3(GR_FL_WG), 0, c->stream>>>(c->frames, c->frame_stride, slot_bytes, s0, nb, sel, form, vd, S, f->n ? 1u : 0u);
             HIPCHK(c, hipGetLastError());
             ++f->launches; f->last_wx = wx; f->last_check = check;
-            HIPCHK(c, hipMemcpyAsync(vh, vd, nb * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
+            st = V.end(c, nb); if (st) return st;
         }
         for (uint32_t k = 0; k < nb; ++k) {
-            const int s = grb::close_frame(c, fe, pre, k, status_out, [&] { return vh[k] != GR_NOIDX ? fail(c, GR_E_NO_POSITION, "atom has no position", vh[k]) : (int)GR_OK; });
+            const int s = grb::close_frame(c, fe, pre, k, status_out, [&] { return V.judge(c, k); });
             if (s == GR_OK) ++f->n;
         }
     }
@@ -352,44 +307,24 @@ gr_fluct *gr_fluct_create(gr_ctx *c, const char *group, int *status) try {
     if (c->frame_stride * sizeof(float) >= GR_BUF_NOWHERE) { *status = fail(c, GR_E_INVALID_ARG, "fluctuations: a slot of this system is too large for a buffer resource"); return nullptr; }
     std::unique_ptr<gr_fluct> f(new gr_fluct());
     f->c = c; f->group = group;
-    f->atoms = hb_group_atoms(*g);
-    f->n_atoms = (uint32_t)f->atoms.size();
-    const uint32_t a0 = f->atoms.front(), span = f->atoms.back() - a0 + 1u;
-    f->form = span == f->n_atoms ? 0 : (2ull * f->n_atoms >= span ? 2 : 1);
-    f->units = f->form == 1 ? f->n_atoms : ((a0 + span - 1u) >> 2) - (a0 >> 2) + 1u;
-    f->upad = (f->units + GR_FL_WG - 1u) & ~(GR_FL_WG - 1u);
     (void)hipSetDevice(c->device);
+    bool ok = f->snap.build(c, hb_group_atoms(*g)) && f->verdicts.reserve(2u * GR_FL_AHEAD);
+    f->n_atoms = (uint32_t)f->snap.atoms.size();
+    f->upad = (f->snap.units + GR_FL_WG - 1u) & ~(GR_FL_WG - 1u);
     const size_t len = fl_state_len(f.get());
-    bool ok = f->atoms_dev.reserve(f->n_atoms, grbuf::exact) == hipSuccess && f->o.reserve(len, grbuf::exact) == hipSuccess && f->s.reserve(len, grbuf::exact) == hipSuccess &&
-              f->q.reserve(len, grbuf::exact) == hipSuccess && f->mean_dev.reserve(3 * (size_t)f->n_atoms, grbuf::exact) == hipSuccess &&
-              f->verdict_dev.reserve(GR_MAX_BATCH + 2u * GR_FL_AHEAD, grbuf::exact) == hipSuccess &&
-              f->verdict_host.reserve(GR_MAX_BATCH + 2u * GR_FL_AHEAD, grbuf::exact) == hipSuccess;
-    ok = ok && hipMemcpy(f->atoms_dev.get(), f->atoms.data(), 4 * (size_t)f->n_atoms, hipMemcpyHostToDevice) == hipSuccess;
-    if (ok && f->form == 2) {
-        std::vector<uint32_t> bits(((size_t)c->n_pad + 31) / 32, 0u);
-        for (uint32_t a : f->atoms) bits[a >> 5] |= 1u << (a & 31u);
-        ok = f->mask_dev.reserve(bits.size(), grbuf::exact) == hipSuccess && hipMemcpy(f->mask_dev.get(), bits.data(), 4 * bits.size(), hipMemcpyHostToDevice) == hipSuccess;
-    }
+    ok = ok && f->o.reserve(len, grbuf::exact) == hipSuccess && f->s.reserve(len, grbuf::exact) == hipSuccess && f->q.reserve(len, grbuf::exact) == hipSuccess &&
+         f->mean_dev.reserve(3 * (size_t)f->n_atoms, grbuf::exact) == hipSuccess;
     ok = ok && fl_zero(f.get()) == GR_OK && hipStreamSynchronize(c->stream) == hipSuccess;
     if (!ok) {
         (void)hipGetLastError();
         *status = fail(c, GR_E_HIP, "fluctuations: device allocation failed");
         return nullptr;
     }
-    // the snapshot as a selection of its own: the group may be replaced or removed while the object lives
-    GrSel &s = f->sel;
-    s.n = f->n_atoms; s.contiguous = f->form == 0 ? 1u : 0u; s.start = a0; s.g0 = a0 >> 8; s.idx = f->atoms_dev.get();
-    s.masked = f->form == 2 ? 1u : 0u; s.span = span; s.mask = f->form == 2 ? f->mask_dev.get() : nullptr;
     *status = GR_OK;
     return f.release();
 } catch (...) { if (status) *status = gr_abi_guard(); return nullptr; }
 
-void gr_fluct_destroy(gr_fluct *f) try {
-    if (!f) return;
-    (void)hipSetDevice(f->c->device);
-    (void)hipStreamSynchronize(f->c->stream);
-    delete f;                                              // (frees the grow-only buffers)
-} catch (...) { }
+void gr_fluct_destroy(gr_fluct *f) try { gr_object_destroy(f); } catch (...) { }
 
 int gr_fluct_accumulate_batch(gr_fluct *f, uint32_t first_slot, uint32_t n_frames, int *status_out) try {
     if (!f) return GR_E_INVALID_ARG;
@@ -479,7 +414,7 @@ int gr_fluct_store_mean(gr_fluct *f, gr_ctx *dst, uint32_t slot) try {
     HIPCHK(c, hipMemcpy(f->mean_dev.get(), mean.data(), mean.size() * sizeof(float), hipMemcpyHostToDevice));
     {
         SlotUse use(dst, slot);
-        k_fl_store_mean<<<dim3((f->n_atoms + 255u) / 256u), dim3(256), 0, dst->stream>>>(dst->frames + (size_t)slot * dst->frame_stride, f->atoms_dev.get(), f->mean_dev.get(), f->n_atoms);
+        k_fl_store_mean<<<dim3((f->n_atoms + 255u) / 256u), dim3(256), 0, dst->stream>>>(dst->frames + (size_t)slot * dst->frame_stride, f->snap.atoms_dev.get(), f->mean_dev.get(), f->n_atoms);
         HIPCHK(c, hipGetLastError());
     }
     HIPCHK(c, hipStreamSynchronize(dst->stream));         // (the next call may rewrite mean_dev)
@@ -498,7 +433,7 @@ int gr_fluct_stat(const gr_fluct *f, int key, uint64_t *value) try {
     case GR_FL_STAT_LAUNCHES: *value = f->launches; return GR_OK;
     case GR_FL_STAT_LAST_RANGE_GROUPS: *value = f->last_wx; return GR_OK;
     case GR_FL_STAT_LAST_CHECK_GROUPS: *value = f->last_check; return GR_OK;
-    case GR_FL_STAT_FORM: *value = (uint64_t)f->form; return GR_OK;
+    case GR_FL_STAT_FORM: *value = (uint64_t)f->snap.form; return GR_OK;
     case GR_FL_STAT_AHEAD: *value = GR_FL_AHEAD; return GR_OK;
     default: return GR_E_INVALID_ARG;
     }

@@ -10,7 +10,7 @@
 //   axis (i, j), a          (d(i->j).a) / |d(i->j)|, 0 when |d| = 0
 // Every product and sum of these formulas is rounded on its own (ic_value is compiled with contraction off), so a value's bits do not
 // depend on what the kernel does with it afterwards: `accumulate` adds the bits `values` stores.
-//   k_fl_check   (gr_fluct.h, index-list form over the UNIQUE atoms the tuples name) the lowest atom without position, per frame
+//   k_fl_check   (gr_series.h, index-list form over the UNIQUE atoms the tuples name) the lowest atom without position, per frame
 //   k_ic_walk    <KIND, PBC, ACC>: one wave per workgroup, one tuple per lane.  The tuple table is uint32 [arity][T_pad] on the device, so a
 //                wave's index loads are contiguous.  A lane loads its 2 .. 4 atom indices once, turns them into 6 .. 12 byte offsets
 //                (gr_tile_index * 4) and walks its frames with the loads of GR_IC_AHEAD frames in flight.  Buffer loads: the frame's slot
@@ -48,11 +48,8 @@ struct gr_internals {
     int kind = 0;
     uint32_t flags = 0, arity = 0, T = 0, tpad = 0;
     float axis[3] = { 0.0f, 0.0f, 0.0f };
-    std::vector<uint32_t> tuples;         // [T][arity], the caller's order
-    std::vector<uint32_t> uniq;           // the atoms the tuples name, ascending, each once
-    GrSel sel = {};                       // ... as an index list for k_fl_check
-    grbuf::Dev<uint32_t> table_dev, uniq_dev, verdict_dev;      // [arity][T_pad], [unique], [GR_MAX_BATCH + 2 AHEAD]
-    grbuf::Pinned<uint32_t> verdict_host;
+    GrTuples tab;                         // the tuples, the atoms they name, the device table [arity][T_pad]
+    GrVerdicts verdicts;
     grbuf::Dev<float> o, ws;              // [T_pad]; values_batch's workspace
     grbuf::Dev<double> s, q;              // [T_pad]
     uint64_t n = 0;                       // frames counted by accumulate
@@ -262,26 +259,6 @@ uint32_t ic_chunk(const gr_internals *ic, uint32_t wx, uint32_t nf) {
     return (nf + wy - 1u) / wy;
 }
 
-// the segment's verdicts before the check kernel: clean where the host checks passed, "skip" elsewhere and behind the last frame
-void ic_verdicts(gr_internals *ic, const grb::Prechecks &pre, uint32_t nb) {
-    uint32_t *vh = ic->verdict_host.get();
-    for (uint32_t k = 0; k < nb; ++k) vh[k] = pre.ok(k) ? GR_NOIDX : GR_FL_SKIP;
-    for (uint32_t k = nb; k < nb + 2u * GR_IC_AHEAD; ++k) vh[k] = GR_FL_SKIP;
-}
-
-int ic_check_launch(gr_internals *ic, uint32_t s0, uint32_t nb) {
-    gr_ctx *c = ic->c;
-    HIPCHK(c, hipMemcpyAsync(ic->verdict_dev.get(), ic->verdict_host.get(), (nb + 2u * GR_IC_AHEAD) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    const uint32_t check = std::min<uint32_t>(((uint32_t)ic->uniq.size() + 255u) / 256u, GR_FL_CHECK_WGS);
-    k_fl_check<<<dim3(check, nb), dim3(256), 0, c->stream>>>(c->frames, c->frame_stride, s0, ic->sel, 1, ic->verdict_dev.get());
-    ic->last_check = check;
-    return GR_OK;
-}
-
-int ic_judge(gr_ctx *c, uint32_t verdict) {
-    return verdict != GR_NOIDX ? fail(c, GR_E_NO_POSITION, "atom has no position", verdict) : (int)GR_OK;
-}
-
 // out_dev (rows ld floats apart) or out_host ([n_frames][T]); exactly one of them
 int ic_values(gr_internals *ic, uint32_t first_slot, uint32_t n_frames, float *out_host, float *out_dev, uint64_t ld, int *status_out) {
     gr_ctx *c = ic->c;
@@ -291,7 +268,8 @@ int ic_values(gr_internals *ic, uint32_t first_slot, uint32_t n_frames, float *o
     const uint32_t slot_bytes = (uint32_t)(c->frame_stride * sizeof(float));
     const GrIcState none = { nullptr, nullptr, nullptr };
     const ic_kernel_t kernel = ic_kernel<false>(ic->kind, pbc);
-    uint32_t *vh = ic->verdict_host.get(), *vd = ic->verdict_dev.get();
+    GrVerdicts &V = ic->verdicts;
+    const uint32_t *vd = V.dev.get();
     // host variant: frames per piece of the workspace
     const uint32_t piece = (uint32_t)std::max<size_t>(1u, std::min<size_t>(GR_MAX_BATCH, GR_IC_MAX_WS_BYTES / ((size_t)ic->tpad * sizeof(float))));
     if (out_host && ic->ws.reserve((size_t)std::min(piece, n_frames) * ic->tpad, grbuf::exact) != hipSuccess) {
@@ -301,17 +279,17 @@ int ic_values(gr_internals *ic, uint32_t first_slot, uint32_t n_frames, float *o
     grb::FirstError<gr_ctx> fe;
     for (const auto [b0, nb, s0] : grb::Segments{ first_slot, n_frames }) {
         const grb::Prechecks pre(c, { b0, nb, s0 }, box_checks(c, pbc));
-        ic_verdicts(ic, pre, nb);
         {
             SlotUse use(c, s0, nb);
-            st = ic_check_launch(ic, s0, nb); if (st) return st;
+            st = V.begin(c, pre, nb); if (st) return st;
+            ic->last_check = V.check(c, ic->tab.uniq, s0, nb);
             const uint32_t wx = ic_ranges(ic);
             for (uint32_t p0 = 0; p0 < nb; p0 += out_host ? piece : nb) {
                 const uint32_t np = out_host ? std::min(piece, nb - p0) : nb;
                 const uint32_t chunk = ic_chunk(ic, wx, np), wy = (np + chunk - 1u) / chunk;
                 float *rows = out_host ? ic->ws.get() : out_dev + (size_t)b0 * ld;
                 const size_t row_ld = out_host ? ic->tpad : (size_t)ld;
-                kernel<<<dim3(wx, wy), dim3(GR_IC_WG), 0, c->stream>>>(c->frames, c->frame_stride, slot_bytes, s0 + p0, np, ic->table_dev.get(), ic->T, ic->tpad,
+                kernel<<<dim3(wx, wy), dim3(GR_IC_WG), 0, c->stream>>>(c->frames, c->frame_stride, slot_bytes, s0 + p0, np, ic->tab.table_dev.get(), ic->T, ic->tpad,
                                                                        c->boxes_dev, vd + p0, ic->axis[0], ic->axis[1], ic->axis[2], chunk, rows, row_ld, none, 0u);
                 HIPCHK(c, hipGetLastError());
                 ++ic->launches; ic->last_wx = wx; ic->last_wy = wy;
@@ -320,10 +298,9 @@ int ic_values(gr_internals *ic, uint32_t first_slot, uint32_t n_frames, float *o
                     HIPCHK(c, hipMemcpy2D(out_host + (size_t)(b0 + p0) * ic->T, ic->T * sizeof(float), rows, row_ld * sizeof(float), ic->T * sizeof(float), np, hipMemcpyDeviceToHost));
                 }
             }
-            HIPCHK(c, hipMemcpyAsync(vh, vd, nb * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
+            st = V.end(c, nb); if (st) return st;
         }
-        for (uint32_t k = 0; k < nb; ++k) grb::close_frame(c, fe, pre, k, status_out, [&] { return ic_judge(c, vh[k]); });
+        for (uint32_t k = 0; k < nb; ++k) grb::close_frame(c, fe, pre, k, status_out, [&] { return V.judge(c, k); });
     }
     return fe.finish(c);
 }
@@ -336,24 +313,24 @@ int ic_accumulate(gr_internals *ic, uint32_t first_slot, uint32_t n_frames, int 
     const uint32_t slot_bytes = (uint32_t)(c->frame_stride * sizeof(float));
     const GrIcState S = { ic->o.get(), ic->s.get(), ic->q.get() };
     const ic_kernel_t kernel = ic_kernel<true>(ic->kind, pbc);
-    uint32_t *vh = ic->verdict_host.get(), *vd = ic->verdict_dev.get();
+    GrVerdicts &V = ic->verdicts;
+    const uint32_t *vd = V.dev.get();
     grb::FirstError<gr_ctx> fe;
     for (const auto [b0, nb, s0] : grb::Segments{ first_slot, n_frames }) {
         const grb::Prechecks pre(c, { b0, nb, s0 }, box_checks(c, pbc));
-        ic_verdicts(ic, pre, nb);
         if (pre.any_ok) {
             SlotUse use(c, s0, nb);
-            st = ic_check_launch(ic, s0, nb); if (st) return st;
+            st = V.begin(c, pre, nb); if (st) return st;
+            ic->last_check = V.check(c, ic->tab.uniq, s0, nb);
             const uint32_t wx = ic_ranges(ic);
-            kernel<<<dim3(wx), dim3(GR_IC_WG), 0, c->stream>>>(c->frames, c->frame_stride, slot_bytes, s0, nb, ic->table_dev.get(), ic->T, ic->tpad, c->boxes_dev, vd,
+            kernel<<<dim3(wx), dim3(GR_IC_WG), 0, c->stream>>>(c->frames, c->frame_stride, slot_bytes, s0, nb, ic->tab.table_dev.get(), ic->T, ic->tpad, c->boxes_dev, vd,
                                                                ic->axis[0], ic->axis[1], ic->axis[2], nb, nullptr, 0, S, ic->n ? 1u : 0u);
             HIPCHK(c, hipGetLastError());
             ++ic->launches; ic->last_wx = wx; ic->last_wy = 1u;
-            HIPCHK(c, hipMemcpyAsync(vh, vd, nb * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
+            st = V.end(c, nb); if (st) return st;
         }
         for (uint32_t k = 0; k < nb; ++k) {
-            const int s = grb::close_frame(c, fe, pre, k, status_out, [&] { return ic_judge(c, vh[k]); });
+            const int s = grb::close_frame(c, fe, pre, k, status_out, [&] { return V.judge(c, k); });
             if (s == GR_OK) ++ic->n;
         }
     }
@@ -381,49 +358,20 @@ gr_internals *gr_internals_create(gr_ctx *c, int kind, const uint64_t *atoms, ui
         if (!std::isfinite(len) || !(len > 0.0)) { *status = fail(c, GR_E_INVALID_ARG, "internals: the axis is zero or not finite"); return nullptr; }
         ic->axis[0] = (float)(x / len); ic->axis[1] = (float)(y / len); ic->axis[2] = (float)(z / len);
     }
-    const uint32_t A = ic->arity;
-    ic->tuples.resize((size_t)ic->T * A);
-    for (uint64_t t = 0; t < n_tuples; ++t) {
-        for (uint32_t a = 0; a < A; ++a) {
-            const uint64_t i = atoms[t * A + a];
-            if (i >= c->n) { *status = fail(c, GR_E_OUT_OF_RANGE, "internals: atom index out of range", i); return nullptr; }
-            for (uint32_t b = 0; b < a; ++b)
-                if (atoms[t * A + b] == i) { *status = fail(c, GR_E_INVALID_ARG, "internals: an atom appears twice in one tuple", t); return nullptr; }
-            ic->tuples[t * A + a] = (uint32_t)i;
-        }
-    }
-    ic->uniq = ic->tuples;
-    std::sort(ic->uniq.begin(), ic->uniq.end());
-    ic->uniq.erase(std::unique(ic->uniq.begin(), ic->uniq.end()), ic->uniq.end());
-    std::vector<uint32_t> table((size_t)A * ic->tpad, 0u);
-    for (uint32_t t = 0; t < ic->T; ++t)
-        for (uint32_t a = 0; a < A; ++a) table[(size_t)a * ic->tpad + t] = ic->tuples[(size_t)t * A + a];
-    (void)hipSetDevice(c->device);
-    bool ok = ic->table_dev.reserve(table.size(), grbuf::exact) == hipSuccess && ic->uniq_dev.reserve(ic->uniq.size(), grbuf::exact) == hipSuccess &&
-              ic->o.reserve(ic->tpad, grbuf::exact) == hipSuccess && ic->s.reserve(ic->tpad, grbuf::exact) == hipSuccess && ic->q.reserve(ic->tpad, grbuf::exact) == hipSuccess &&
-              ic->verdict_dev.reserve(GR_MAX_BATCH + 2u * GR_IC_AHEAD, grbuf::exact) == hipSuccess &&
-              ic->verdict_host.reserve(GR_MAX_BATCH + 2u * GR_IC_AHEAD, grbuf::exact) == hipSuccess;
-    ok = ok && hipMemcpy(ic->table_dev.get(), table.data(), 4 * table.size(), hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(ic->uniq_dev.get(), ic->uniq.data(), 4 * ic->uniq.size(), hipMemcpyHostToDevice) == hipSuccess;
+    *status = ic->tab.build(c, "internals", "an atom appears twice in one tuple", atoms, n_tuples, ic->arity, ic->tpad); if (*status) return nullptr;
+    bool ok = ic->verdicts.reserve(2u * GR_IC_AHEAD) && ic->o.reserve(ic->tpad, grbuf::exact) == hipSuccess && ic->s.reserve(ic->tpad, grbuf::exact) == hipSuccess &&
+              ic->q.reserve(ic->tpad, grbuf::exact) == hipSuccess;
     ok = ok && ic_zero(ic.get()) == GR_OK && hipStreamSynchronize(c->stream) == hipSuccess;
     if (!ok) {
         (void)hipGetLastError();
         *status = fail(c, GR_E_HIP, "internals: device allocation failed");
         return nullptr;
     }
-    GrSel &s = ic->sel;
-    s.n = (uint32_t)ic->uniq.size(); s.contiguous = 0u; s.start = ic->uniq.front(); s.g0 = s.start >> 8; s.idx = ic->uniq_dev.get();
-    s.masked = 0u; s.span = ic->uniq.back() - s.start + 1u; s.mask = nullptr;
     *status = GR_OK;
     return ic.release();
 } catch (...) { if (status) *status = gr_abi_guard(); return nullptr; }
 
-void gr_internals_destroy(gr_internals *ic) try {
-    if (!ic) return;
-    (void)hipSetDevice(ic->c->device);
-    (void)hipStreamSynchronize(ic->c->stream);
-    delete ic;                                             // (frees the grow-only buffers)
-} catch (...) { }
+void gr_internals_destroy(gr_internals *ic) try { gr_object_destroy(ic); } catch (...) { }
 
 uint64_t gr_internals_count(const gr_internals *ic) { return ic ? ic->T : 0u; }
 uint64_t gr_internals_frames(const gr_internals *ic) { return ic ? ic->n : 0u; }
@@ -489,7 +437,7 @@ int gr_internals_merge(gr_internals *dst, gr_internals *src) try {
     int st = busy_check(c); if (st) return st;
     if (src->c != c) { st = busy_check(src->c); if (st) return fail(c, st, src->c->err); }
     if (src == dst) return fail(c, GR_E_INVALID_ARG, "internals: an object cannot be merged into itself");
-    if (dst->kind != src->kind || dst->flags != src->flags || dst->T != src->T || dst->tuples != src->tuples || memcmp(dst->axis, src->axis, sizeof dst->axis) != 0) {
+    if (dst->kind != src->kind || dst->flags != src->flags || dst->T != src->T || dst->tab.tuples != src->tab.tuples || memcmp(dst->axis, src->axis, sizeof dst->axis) != 0) {
         c->counts[0] = dst->T; c->counts[1] = src->T;
         return fail(c, GR_E_INCONSISTENT_GROUP, "internals: the objects differ in kind, flags, axis or tuples");
     }
@@ -529,7 +477,7 @@ int gr_internals_stat(const gr_internals *ic, int key, uint64_t *value) try {
     case GR_IC_STAT_LAST_FRAME_GROUPS: *value = ic->last_wy; return GR_OK;
     case GR_IC_STAT_LAST_CHECK_GROUPS: *value = ic->last_check; return GR_OK;
     case GR_IC_STAT_ARITY: *value = ic->arity; return GR_OK;
-    case GR_IC_STAT_UNIQUE_ATOMS: *value = ic->uniq.size(); return GR_OK;
+    case GR_IC_STAT_UNIQUE_ATOMS: *value = ic->tab.uniq.atoms.size(); return GR_OK;
     case GR_IC_STAT_AHEAD: *value = GR_IC_AHEAD; return GR_OK;
     default: return GR_E_INVALID_ARG;
     }

@@ -21,7 +21,7 @@
 // the shorter way round.  A FAILED frame (an atom of the group without position; with NOJUMP a frame without a usable box) still takes
 // a time index: its row is zeros, its ok 0, it enters no pair, the walk skips it (w and u stay) and the next good frame is unwrapped
 // against the last good one.
-//   k_fl_check    (gr_fluct.h, unchanged) the first atom of the group without position, per frame
+//   k_fl_check    (gr_series.h) the first atom of the group without position, per frame
 //   k_msd_walk    k_fl_accumulate's walk: a lane owns ONE atom of the snapshot for the launch and takes the segment's frames in ascending
 //                 order, the rows of GR_FL_AHEAD frames in flight (buffer loads, no load under a condition), and writes its atoms' panel
 //                 entries: consecutive lanes hold consecutive atoms, every component of every frame is one contiguous store per wave.
@@ -29,28 +29,19 @@
 //                 in group order whatever the form, so the row form of Fluctuations (four atoms per lane in slot order) would have to
 //                 scatter its stores and compact masked spans; one walk, one order, and the three forms give the same bits by construction.
 //   k_msd_norms   one workgroup per appended frame: q[t] by a fixed-order block sum (gr_block_sum), ok[t]
-//   k_msd_gram    G = X X^T on v_mfma_f64_16x16x4_f64 (widened f32 operands: exact products, f64 sums) for the 64 x 64 blocks of frame
-//                 pairs with block-row <= block-column that touch the band t' - t <= max_lag -- no other block is enumerated.  Wave (wr, wc)
-//                 of a workgroup owns a 32 x 32 quarter (2 x 2 tiles) as in k_cv_product; the contraction runs over the 3 n_pad values of a
-//                 row in trips of GR_MSD_TRIP = 16, ascending, operands straight from the panel (L2 / L1), GR_MSD_AHEAD trips in flight.  Every entry belongs to ONE wave
-//                 and is ONE chain of MFMAs: its bits depend on its two rows and n_pad alone.  The block then forms D2 = q_t + q_t' - 2 G
-//                 for its valid pairs (ok on both sides, t < t', t' - t <= max_lag; D2(t, t) IS DEFINED AS 0, so msd[0] is exactly 0 -- the
-//                 chain of G(t, t) and the block sum of q_t are two orders of the same sum and differ by rounding) into LDS, and 127 lanes
-//                 add one diagonal of the block each, rows ascending: the per-diagonal partial sums of the block.
-//   k_msd_lags    one lane per lag: the partials of that lag in ascending block-row order (per block row: the nearer block column first).
+//   k_band_gram<true>, k_band_lags   (gr_band.h, shared with VectorCorrelation) the band product: D2 = q_t + q_t' - 2 G over the 64 x 64
+//                 blocks of frame pairs that touch the band t' - t <= max_lag, G = X X^T on the matrix cores, every entry ONE chain of
+//                 ONE wave; the blocks' diagonals are added in a fixed order, then the blocks of a lag.  D2(t, t) IS DEFINED AS 0, so
+//                 msd[0] is exactly 0.
 // No atomic decides a sum.  o, w, u, the panel and q are a function of the SEQUENCE of appended frames alone -- not of how they were cut
 // into calls, 1024-frame segments or grids; sum[tau] is a function of the panel (and so is a prefix of the full curve's for any max_lag).
 // The pair counts are integer work on the ok flags, done on the host.  CAP: capacity x 3 x n_pad x 4 B <= GR_MSD_MAX_PANEL_BYTES.
 #pragma once
+#include "gr_band.h"
 #include "gr_fluct.h"
 
 #if defined(__HIPCC__)
 
-#define GR_MSD_BLOCK 64u                  /* edge of a block of the Gram matrix, in frames */
-#define GR_MSD_TRIP 16u                   /* panel values per trip of the product: one float4 per lane and operand row, four MFMAs */
-#define GR_MSD_AHEAD 3u                   /* trips whose operands a wave of the product has in flight */
-#define GR_MSD_DIAGS (2u * GR_MSD_BLOCK - 1u)      /* diagonals of a block: t' - t = -63 .. 63 inside it */
-#define GR_MSD_LD (GR_MSD_BLOCK + 1u)     /* doubles per row of the block in LDS (odd: a diagonal's lanes read consecutive banks) */
 #define GR_MSD_MAX_WALK (1u << 22)        /* k_msd_walk's grid at most */
 #define GR_MSD_DIMS (GR_MSD_X | GR_MSD_Y | GR_MSD_Z)
 
@@ -63,37 +54,25 @@ struct GrMsdState {
 struct gr_msd {
     gr_ctx *c = nullptr;
     std::string group;
-    std::vector<uint32_t> atoms;          // the snapshot, group order (ascending)
-    uint32_t n_atoms = 0, n_pad = 0, units = 0, capacity = 0, flags = 0;
-    int form = 0;                         // as Fluctuations': how k_fl_check walks the snapshot (the walk itself takes the index list)
-    GrSel sel = {};
-    grbuf::Dev<uint32_t> atoms_dev, mask_dev, verdict_dev, ok_dev;        // ..., [capacity]
-    grbuf::Pinned<uint32_t> verdict_host;
+    GrSnapshot snap;                      // the group's atoms at create (the check walks it in its form, the walk takes the index list)
+    GrVerdicts verdicts;
+    uint32_t n_atoms = 0, n_pad = 0, capacity = 0, flags = 0;
+    grbuf::Dev<uint32_t> ok_dev;          // [capacity]
     grbuf::Dev<float> o, w, X;            // [3][n_pad], [3][n_pad], [capacity][3][n_pad]
     grbuf::Dev<double> u, q;              // [3][n_pad], [capacity]
-    grbuf::Dev<double> part, sums;        // compute: [blocks][GR_MSD_DIAGS], [lags]
+    GrBandWork band;                      // compute
     std::vector<uint8_t> ok_host;         // [frames]
     uint32_t frames = 0;                  // time indices taken
     uint64_t n_good = 0;                  // counted frames
     bool computed = false;
     std::vector<double> sum_host;         // [lags] of the last compute
     std::vector<uint64_t> pairs_host;
-    uint32_t walk_groups = 0, gram_groups = 0;        // gr_msd_set_launch; 0: the default
-    uint32_t last_walk = 0, last_gram = 0;
-    uint64_t launches = 0, blocks = 0;
+    uint32_t walk_groups = 0;             // gr_msd_set_launch; 0: the default
+    uint32_t last_walk = 0;
+    uint64_t launches = 0;
 };
 
-typedef double gr_msd_d4 __attribute__((ext_vector_type(4)));
-
 namespace {
-
-// block rows 0 .. r0 - 1 (r0 = nblk - W) hold W + 1 blocks (columns bi .. bi + W), row bi >= r0 holds nblk - bi
-__host__ __device__ __forceinline__ uint32_t msd_block_index(uint32_t bi, uint32_t db, uint32_t nblk, uint32_t W) {
-    const uint32_t r0 = nblk - W;
-    if (bi < r0) return bi * (W + 1u) + db;
-    const uint32_t k = bi - r0;           // short rows in front of this one: W, W - 1, ... blocks
-    return r0 * (W + 1u) + k * W - (k * (k - 1u)) / 2u + db;
-}
 
 // frames [s0, s0 + nf) of `frames` -> rows 0 .. nf - 1 of X (the caller passes the panel's next rows); verdict as k_fl_accumulate
 __global__ __launch_bounds__(GR_FL_WG) void k_msd_walk(const float *__restrict__ frames, size_t stride, uint32_t slot_bytes, uint32_t s0, uint32_t nf,
@@ -210,108 +189,6 @@ __global__ __launch_bounds__(GR_WG) void k_msd_norms(const float *__restrict__ X
     }
 }
 
-// block t of the band -> part[t][GR_MSD_DIAGS]; T frames, K = 3 n_pad values per row, nblk block rows, W = the farthest block column of a row
-__global__ __launch_bounds__(256) void k_msd_gram(const float *__restrict__ X, const double *__restrict__ q, const uint32_t *__restrict__ ok, uint32_t T, uint32_t K,
-                                                  uint32_t nblk, uint32_t W, uint32_t nblocks, uint32_t max_lag, double *__restrict__ part) {
-    __shared__ double D[GR_MSD_BLOCK * GR_MSD_LD];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, m = lane & 15u, kg = lane >> 4;
-    const uint32_t wr = wave >> 1, wc = wave & 1u;
-    const uint32_t trips = K / GR_MSD_TRIP;
-    const uint32_t r0 = nblk - W;
-    for (uint32_t t = blockIdx.x; t < nblocks; t += gridDim.x) {
-        uint32_t bi, db;
-        if (t < r0 * (W + 1u)) { bi = t / (W + 1u); db = t % (W + 1u); }
-        else {
-            uint32_t rem = t - r0 * (W + 1u);
-            bi = r0;
-            while (rem >= nblk - bi) { rem -= nblk - bi; ++bi; }
-            db = rem;
-        }
-        const uint32_t bj = bi + db;
-        gr_msd_d4 acc[2][2];
-#pragma unroll
-        for (uint32_t a = 0; a < 2u; ++a)
-#pragma unroll
-            for (uint32_t b = 0; b < 2u; ++b) acc[a][b] = (gr_msd_d4){ 0.0, 0.0, 0.0, 0.0 };
-        // (the quarter below the diagonal of a diagonal block holds no valid pair: its wave waits)
-        if (!(bi == bj && wr > wc)) {
-            // operand rows of this lane: tile a of A holds frames 64 bi + 32 wr + 16 a + m, tile b of B frames 64 bj + 32 wc + 16 b + m; a frame
-            // beyond the panel's last is read as the last (never closed)
-            const float *pa[2], *pb[2];
-#pragma unroll
-            for (uint32_t a = 0; a < 2u; ++a) {
-                pa[a] = X + (size_t)min(GR_MSD_BLOCK * bi + 32u * wr + 16u * a + m, T - 1u) * K + 4u * kg;
-                pb[a] = X + (size_t)min(GR_MSD_BLOCK * bj + 32u * wc + 16u * a + m, T - 1u) * K + 4u * kg;
-            }
-            // the operands of GR_MSD_AHEAD trips are in flight (behind the last trip: the last trip's again, never used); the MFMAs keep
-            // the ascending order of the trips
-            float4 a4[GR_MSD_AHEAD][2], b4[GR_MSD_AHEAD][2];
-#pragma unroll
-            for (uint32_t p = 0; p < GR_MSD_AHEAD; ++p) {
-                const size_t at = (size_t)min(p, trips - 1u) * GR_MSD_TRIP;
-#pragma unroll
-                for (uint32_t a = 0; a < 2u; ++a) { a4[p][a] = *reinterpret_cast<const float4 *>(pa[a] + at); b4[p][a] = *reinterpret_cast<const float4 *>(pb[a] + at); }
-            }
-            for (uint32_t g0 = 0; g0 < trips; g0 += GR_MSD_AHEAD) {
-#pragma unroll
-                for (uint32_t p = 0; p < GR_MSD_AHEAD; ++p) {
-                    const uint32_t g = g0 + p;
-                    if (g >= trips) break;                          // (the same in every lane)
-                    const float av[2][4] = { { a4[p][0].x, a4[p][0].y, a4[p][0].z, a4[p][0].w }, { a4[p][1].x, a4[p][1].y, a4[p][1].z, a4[p][1].w } };
-                    const float bv[2][4] = { { b4[p][0].x, b4[p][0].y, b4[p][0].z, b4[p][0].w }, { b4[p][1].x, b4[p][1].y, b4[p][1].z, b4[p][1].w } };
-                    const size_t next = (size_t)min(g + GR_MSD_AHEAD, trips - 1u) * GR_MSD_TRIP;
-#pragma unroll
-                    for (uint32_t a = 0; a < 2u; ++a) { a4[p][a] = *reinterpret_cast<const float4 *>(pa[a] + next); b4[p][a] = *reinterpret_cast<const float4 *>(pb[a] + next); }
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-#pragma unroll
-                        for (int a = 0; a < 2; ++a)
-#pragma unroll
-                            for (int b = 0; b < 2; ++b) acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64((double)av[a][j], (double)bv[b][j], acc[a][b], 0, 0, 0);
-                }
-            }
-        }
-        // C/D map of the f64 form: lane holds column lane & 15, rows (lane >> 4) + 4 p of its tile
-#pragma unroll
-        for (uint32_t a = 0; a < 2u; ++a)
-#pragma unroll
-            for (uint32_t b = 0; b < 2u; ++b) {
-                const uint32_t j = 32u * wc + 16u * b + m, gj = GR_MSD_BLOCK * bj + j, cj = min(gj, T - 1u);
-                const double qj = q[cj];
-                const bool okj = gj < T && ok[cj] != 0u;
-#pragma unroll
-                for (uint32_t p = 0; p < 4u; ++p) {
-                    const uint32_t i = 32u * wr + 16u * a + kg + 4u * p, gi = GR_MSD_BLOCK * bi + i, ci = min(gi, T - 1u);
-                    const bool valid = okj && gi < gj && gj - gi <= max_lag && ok[ci] != 0u;
-                    D[i * GR_MSD_LD + j] = valid ? (q[ci] + qj) - 2.0 * acc[a][b][p] : 0.0;
-                }
-            }
-        __syncthreads();
-        if (threadIdx.x < GR_MSD_DIAGS) {
-            // diagonal j - i = threadIdx.x - 63 of the block, rows ascending
-            const uint32_t dl = threadIdx.x;
-            const uint32_t i0 = dl < GR_MSD_BLOCK - 1u ? GR_MSD_BLOCK - 1u - dl : 0u, i1 = dl > GR_MSD_BLOCK - 1u ? GR_MSD_DIAGS - dl : GR_MSD_BLOCK;
-            double s = 0.0;
-            for (uint32_t i = i0; i < i1; ++i) s += D[i * GR_MSD_LD + i + dl - (GR_MSD_BLOCK - 1u)];
-            part[(size_t)t * GR_MSD_DIAGS + dl] = s;
-        }
-        __syncthreads();
-    }
-}
-
-// lag tau = 64 d0 + r: diagonal r of the blocks (bi, bi + d0) and diagonal r - 64 of the blocks (bi, bi + d0 + 1), block rows ascending
-__global__ __launch_bounds__(256) void k_msd_lags(const double *__restrict__ part, uint32_t nblk, uint32_t W, uint32_t lags, double *__restrict__ sums) {
-    const uint32_t tau = blockIdx.x * 256u + threadIdx.x;
-    if (tau >= lags) return;
-    const uint32_t d0 = tau / GR_MSD_BLOCK, r = tau % GR_MSD_BLOCK;
-    double s = 0.0;
-    for (uint32_t bi = 0; bi < nblk; ++bi) {
-        if (d0 <= W && bi + d0 < nblk) s += part[(size_t)msd_block_index(bi, d0, nblk, W) * GR_MSD_DIAGS + (GR_MSD_BLOCK - 1u) + r];
-        if (r >= 1u && d0 + 1u <= W && bi + d0 + 1u < nblk) s += part[(size_t)msd_block_index(bi, d0 + 1u, nblk, W) * GR_MSD_DIAGS + r - 1u];
-    }
-    sums[tau] = s;
-}
-
 size_t msd_state_len(const gr_msd *m) { return 3u * (size_t)m->n_pad; }
 size_t msd_row_len(const gr_msd *m) { return 3u * (size_t)m->n_pad; }
 
@@ -335,34 +212,31 @@ int msd_append(gr_msd *m, uint32_t first_slot, uint32_t n_frames, int *status_ou
     const uint32_t slot_bytes = (uint32_t)(c->frame_stride * sizeof(float));
     const GrMsdState S = { m->o.get(), m->w.get(), m->u.get(), m->n_pad };
     const uint32_t K = (uint32_t)msd_row_len(m);
-    uint32_t *vh = m->verdict_host.get(), *vd = m->verdict_dev.get();
+    GrVerdicts &V = m->verdicts;
+    const uint32_t *vd = V.dev.get();
     m->computed = false;
     grb::FirstError<gr_ctx> fe;
     for (const auto [b0, nb, s0] : grb::Segments{ first_slot, n_frames }) {
         const grb::Prechecks pre(c, { b0, nb, s0 }, box_checks(c, nojump));
-        for (uint32_t k = 0; k < nb; ++k) vh[k] = pre.ok(k) ? GR_NOIDX : GR_FL_SKIP;
-        for (uint32_t k = nb; k < nb + 2u * GR_FL_AHEAD; ++k) vh[k] = GR_FL_SKIP;
         {
             // (launched even when every frame failed its checks: the rows of failed frames are written as zeros)
             SlotUse use(c, s0, nb);
-            HIPCHK(c, hipMemcpyAsync(vd, vh, (nb + 2u * GR_FL_AHEAD) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-            // launch geometry: one wave per 64 atoms of the padded snapshot, 256 units per workgroup of the check, one workgroup per frame of
-            // the norms; gr_msd_set_launch replaces the number of the walk's ranges
+            st = V.begin(c, pre, nb); if (st) return st;
+            // launch geometry: one wave per 64 atoms of the padded snapshot, one workgroup per frame of the norms; gr_msd_set_launch
+            // replaces the number of the walk's ranges
             const uint32_t wx = std::min<uint32_t>(m->walk_groups ? m->walk_groups : m->n_pad / GR_FL_WG, GR_MSD_MAX_WALK);
-            const uint32_t check = std::min<uint32_t>((m->units + 255u) / 256u, GR_FL_CHECK_WGS);
             const size_t at = (size_t)m->frames + b0;
             float *rows = m->X.get() + at * K;
-            if (pre.any_ok) k_fl_check<<<dim3(check, nb), dim3(256), 0, c->stream>>>(c->frames, c->frame_stride, s0, m->sel, m->form, vd);
-            k_msd_walk<<<dim3(wx), dim3(GR_FL_WG), 0, c->stream>>>(c->frames, c->frame_stride, slot_bytes, s0, nb, m->atoms_dev.get(), m->n_atoms, c->boxes_dev, vd, S,
+            if (pre.any_ok) V.check(c, m->snap, s0, nb);
+            k_msd_walk<<<dim3(wx), dim3(GR_FL_WG), 0, c->stream>>>(c->frames, c->frame_stride, slot_bytes, s0, nb, m->snap.atoms_dev.get(), m->n_atoms, c->boxes_dev, vd, S,
                                                                   m->n_good ? 1u : 0u, m->flags, rows);
             k_msd_norms<<<dim3(nb), dim3(GR_WG), 0, c->stream>>>(rows, K, vd, m->q.get() + at, m->ok_dev.get() + at);
             HIPCHK(c, hipGetLastError());
             ++m->launches; m->last_walk = wx;
-            HIPCHK(c, hipMemcpyAsync(vh, vd, nb * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
+            st = V.end(c, nb); if (st) return st;
         }
         for (uint32_t k = 0; k < nb; ++k) {
-            const int s = grb::close_frame(c, fe, pre, k, status_out, [&] { return vh[k] != GR_NOIDX ? fail(c, GR_E_NO_POSITION, "atom has no position", vh[k]) : (int)GR_OK; });
+            const int s = grb::close_frame(c, fe, pre, k, status_out, [&] { return V.judge(c, k); });
             m->ok_host.push_back(s == GR_OK ? 1 : 0);
             if (s == GR_OK) ++m->n_good;
         }
@@ -376,33 +250,13 @@ int msd_compute(gr_msd *m, uint32_t max_lag) {
     int st = busy_check(c); if (st) return st;
     if (m->frames == 0) return fail(c, GR_E_INVALID_ARG, "msd: no frame has been appended");
     (void)hipSetDevice(c->device);
-    const uint32_t T = m->frames;
-    max_lag = std::min(max_lag, T - 1u);                   // (a lag beyond the last frame has no pair: clamped)
-    const uint32_t lags = max_lag + 1u;
-    const uint32_t nblk = (T + GR_MSD_BLOCK - 1u) / GR_MSD_BLOCK;
-    const uint32_t W = std::min(nblk - 1u, (max_lag + GR_MSD_BLOCK - 1u) / GR_MSD_BLOCK);
-    const uint64_t nblocks = (uint64_t)(nblk - W) * (W + 1u) + (uint64_t)W * (W + 1u) / 2u;
-    if (nblocks > 0x7fffffffull) return fail(c, GR_E_INVALID_ARG, "msd: too many blocks of frame pairs for one compute");
-    if (m->part.reserve((size_t)nblocks * GR_MSD_DIAGS, grbuf::exact) != hipSuccess || m->sums.reserve(lags, grbuf::exact) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(c, GR_E_HIP, "msd: device allocation failed");
-    }
-    uint32_t grid = (uint32_t)nblocks;
-    if (m->gram_groups && m->gram_groups < grid) grid = m->gram_groups;
-    k_msd_gram<<<dim3(grid), dim3(256), 0, c->stream>>>(m->X.get(), m->q.get(), m->ok_dev.get(), T, (uint32_t)msd_row_len(m), nblk, W, (uint32_t)nblocks, max_lag, m->part.get());
-    k_msd_lags<<<dim3((lags + 255u) / 256u), dim3(256), 0, c->stream>>>(m->part.get(), nblk, W, lags, m->sums.get());
-    HIPCHK(c, hipGetLastError());
-    ++m->launches; m->last_gram = grid; m->blocks = nblocks;
-    m->sum_host.assign(lags, 0.0);
-    HIPCHK(c, hipMemcpyAsync(m->sum_host.data(), m->sums.get(), lags * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    // the pair counts meanwhile: integer work on the ok flags
-    m->pairs_host.assign(lags, 0u);
-    const uint8_t *okh = m->ok_host.data();
-    for (uint32_t tau = 0; tau < lags; ++tau) {
-        uint64_t n = 0;
-        for (uint32_t t = 0; t + tau < T; ++t) n += (uint64_t)(okh[t] & okh[t + tau]);
-        m->pairs_host[tau] = n;
-    }
+    grband::Geometry g;
+    st = band_reserve(c, "msd", m->band, m->frames, max_lag, 1u, g); if (st) return st;
+    st = band_launch<true>(c, m->band, g, 1u, m->X.get(), (uint32_t)msd_row_len(m), nullptr, 0u, m->q.get(), m->ok_dev.get(), m->frames); if (st) return st;
+    ++m->launches;
+    m->sum_host.assign(g.lags, 0.0);
+    HIPCHK(c, hipMemcpyAsync(m->sum_host.data(), m->band.sums.get(), g.lags * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    grband::pair_counts(m->ok_host.data(), m->frames, g.lags, m->pairs_host);     // meanwhile
     HIPCHK(c, hipStreamSynchronize(c->stream));
     m->computed = true;
     return GR_OK;
@@ -425,50 +279,31 @@ gr_msd *gr_msd_create(gr_ctx *c, const char *group, uint32_t capacity_frames, ui
     if (c->frame_stride * sizeof(float) >= GR_BUF_NOWHERE) { *status = fail(c, GR_E_INVALID_ARG, "msd: a slot of this system is too large for a buffer resource"); return nullptr; }
     std::unique_ptr<gr_msd> m(new gr_msd());
     m->c = c; m->group = group; m->flags = flags; m->capacity = capacity_frames;
-    m->atoms = hb_group_atoms(*g);
-    m->n_atoms = (uint32_t)m->atoms.size();
+    std::vector<uint32_t> atoms = hb_group_atoms(*g);
+    m->n_atoms = (uint32_t)atoms.size();
     m->n_pad = (m->n_atoms + GR_FL_WG - 1u) & ~(GR_FL_WG - 1u);
     const uint64_t panel_bytes = (uint64_t)capacity_frames * 3u * m->n_pad * sizeof(float);
     if (panel_bytes > GR_MSD_MAX_PANEL_BYTES) {
         *status = fail(c, GR_E_INVALID_ARG, "msd: capacity x 3 x n_pad x 4 B exceeds GR_MSD_MAX_PANEL_BYTES = " + std::to_string((unsigned long long)GR_MSD_MAX_PANEL_BYTES));
         return nullptr;
     }
-    const uint32_t a0 = m->atoms.front(), span = m->atoms.back() - a0 + 1u;
-    m->form = span == m->n_atoms ? 0 : (2ull * m->n_atoms >= span ? 2 : 1);
-    m->units = m->form == 1 ? m->n_atoms : ((a0 + span - 1u) >> 2) - (a0 >> 2) + 1u;
     (void)hipSetDevice(c->device);
     const size_t len = msd_state_len(m.get());
-    bool ok = m->atoms_dev.reserve(m->n_atoms, grbuf::exact) == hipSuccess && m->o.reserve(len, grbuf::exact) == hipSuccess && m->w.reserve(len, grbuf::exact) == hipSuccess &&
-              m->u.reserve(len, grbuf::exact) == hipSuccess && m->X.reserve((size_t)capacity_frames * msd_row_len(m.get()), grbuf::exact) == hipSuccess &&
-              m->q.reserve(capacity_frames, grbuf::exact) == hipSuccess && m->ok_dev.reserve(capacity_frames, grbuf::exact) == hipSuccess &&
-              m->verdict_dev.reserve(GR_MAX_BATCH + 2u * GR_FL_AHEAD, grbuf::exact) == hipSuccess &&
-              m->verdict_host.reserve(GR_MAX_BATCH + 2u * GR_FL_AHEAD, grbuf::exact) == hipSuccess;
-    ok = ok && hipMemcpy(m->atoms_dev.get(), m->atoms.data(), 4 * (size_t)m->n_atoms, hipMemcpyHostToDevice) == hipSuccess;
-    if (ok && m->form == 2) {
-        std::vector<uint32_t> bits(((size_t)c->n_pad + 31) / 32, 0u);
-        for (uint32_t a : m->atoms) bits[a >> 5] |= 1u << (a & 31u);
-        ok = m->mask_dev.reserve(bits.size(), grbuf::exact) == hipSuccess && hipMemcpy(m->mask_dev.get(), bits.data(), 4 * bits.size(), hipMemcpyHostToDevice) == hipSuccess;
-    }
+    bool ok = m->snap.build(c, std::move(atoms)) && m->verdicts.reserve(2u * GR_FL_AHEAD) && m->o.reserve(len, grbuf::exact) == hipSuccess &&
+              m->w.reserve(len, grbuf::exact) == hipSuccess && m->u.reserve(len, grbuf::exact) == hipSuccess &&
+              m->X.reserve((size_t)capacity_frames * msd_row_len(m.get()), grbuf::exact) == hipSuccess && m->q.reserve(capacity_frames, grbuf::exact) == hipSuccess &&
+              m->ok_dev.reserve(capacity_frames, grbuf::exact) == hipSuccess;
     ok = ok && msd_zero(m.get()) == GR_OK && hipStreamSynchronize(c->stream) == hipSuccess;
     if (!ok) {
         (void)hipGetLastError();
         *status = fail(c, GR_E_HIP, "msd: device allocation failed");
         return nullptr;
     }
-    // the snapshot as a selection of its own: the group may be replaced or removed while the object lives
-    GrSel &s = m->sel;
-    s.n = m->n_atoms; s.contiguous = m->form == 0 ? 1u : 0u; s.start = a0; s.g0 = a0 >> 8; s.idx = m->atoms_dev.get();
-    s.masked = m->form == 2 ? 1u : 0u; s.span = span; s.mask = m->form == 2 ? m->mask_dev.get() : nullptr;
     *status = GR_OK;
     return m.release();
 } catch (...) { if (status) *status = gr_abi_guard(); return nullptr; }
 
-void gr_msd_destroy(gr_msd *m) try {
-    if (!m) return;
-    (void)hipSetDevice(m->c->device);
-    (void)hipStreamSynchronize(m->c->stream);
-    delete m;                                              // (frees the grow-only buffers)
-} catch (...) { }
+void gr_msd_destroy(gr_msd *m) try { gr_object_destroy(m); } catch (...) { }
 
 int gr_msd_append_batch(gr_msd *m, uint32_t first_slot, uint32_t n_frames, int *status_out) try {
     if (!m) return GR_E_INVALID_ARG;
@@ -541,7 +376,7 @@ int gr_msd_read_displacements(gr_msd *m, uint32_t t0, uint32_t nt, float *out) t
 
 int gr_msd_set_launch(gr_msd *m, uint32_t walk_groups, uint32_t gram_groups) try {
     if (!m) return GR_E_INVALID_ARG;
-    m->walk_groups = walk_groups; m->gram_groups = gram_groups;
+    m->walk_groups = walk_groups; m->band.gram_groups = gram_groups;
     return GR_OK;
 } catch (...) { return gr_abi_guard(); }
 
@@ -550,10 +385,10 @@ int gr_msd_stat(const gr_msd *m, int key, uint64_t *value) try {
     switch (key) {
     case GR_MSD_STAT_LAUNCHES: *value = m->launches; return GR_OK;
     case GR_MSD_STAT_LAST_WALK_GROUPS: *value = m->last_walk; return GR_OK;
-    case GR_MSD_STAT_LAST_GRAM_GROUPS: *value = m->last_gram; return GR_OK;
-    case GR_MSD_STAT_BLOCK_EDGE: *value = GR_MSD_BLOCK; return GR_OK;
-    case GR_MSD_STAT_TRIP_VALUES: *value = GR_MSD_TRIP; return GR_OK;
-    case GR_MSD_STAT_LAST_BLOCKS: *value = m->blocks; return GR_OK;
+    case GR_MSD_STAT_LAST_GRAM_GROUPS: *value = m->band.last_gram; return GR_OK;
+    case GR_MSD_STAT_BLOCK_EDGE: *value = GR_BAND_BLOCK; return GR_OK;
+    case GR_MSD_STAT_TRIP_VALUES: *value = GR_BAND_TRIP; return GR_OK;
+    case GR_MSD_STAT_LAST_BLOCKS: *value = m->band.blocks; return GR_OK;
     case GR_MSD_STAT_LAGS: *value = m->computed ? m->sum_host.size() : 0u; return GR_OK;
     case GR_MSD_STAT_N_PAD: *value = m->n_pad; return GR_OK;
     case GR_MSD_STAT_COUNTED: *value = m->n_good; return GR_OK;

@@ -20,7 +20,7 @@
 // the pair into a canonical orientation (the lexicographically smaller of (H, Hw) and its transpose), so an entry is a symmetric
 // function of its two frames and of N -- whatever their places in the panels, the neighbours in the block or the run.
 #pragma once
-#include "gr_kernels.h"
+#include "gr_series.h"
 
 #if defined(__HIPCC__)
 
@@ -36,11 +36,13 @@ struct gr_rmsd_panel {
     gr_ctx *c = nullptr;
     std::string group;
     uint32_t n = 0, n_pad = 0, capacity = 0, frames = 0;
-    std::vector<uint32_t> atoms;                 // the snapshot, group order
+    // the group's atoms at create, for the centre stages always as an INDEX LIST (the gather form): a group's sums are then added in the
+    // order of its ordinals whatever its shape in the system (a scattered group gives the bits of the same atoms laid out contiguously)
+    GrSnapshot snap;
     std::vector<float> w_host;                   // their masses
     double W = 0.0;                              // sum of the masses, group order
     uint64_t epoch = 0;                          // context epoch at which the masses were last compared with the snapshot
-    grbuf::Dev<uint32_t> atoms_dev, ok_dev;      // [n], [capacity]
+    grbuf::Dev<uint32_t> ok_dev;                 // [capacity]
     grbuf::Dev<float> w_dev, x;                  // [n_pad], [capacity][3][n_pad]
     grbuf::Dev<double> G;                        // [capacity]
     std::vector<int> status;                     // [frames]
@@ -190,26 +192,17 @@ __global__ __launch_bounds__(256) void k_rp_matrix(const float *__restrict__ xr,
 
 namespace {
 
-// the snapshot as a selection of the centre stages: always the gather form, so that a group's sums are added in the order of its
-// ordinals whatever its shape in the system (a scattered group gives the bits of the same atoms laid out contiguously)
-GrSel rp_sel(const gr_rmsd_panel *p) {
-    GrSel s;
-    s.n = p->n; s.contiguous = 0u; s.start = p->atoms[0]; s.g0 = p->atoms[0] >> 8; s.idx = p->atoms_dev.get();
-    s.masked = 0u; s.span = p->atoms.back() - p->atoms[0] + 1u; s.mask = nullptr;
-    return s;
-}
-
 int rp_append(gr_rmsd_panel *p, uint32_t first_slot, uint32_t n_frames, int *status_out) {
     gr_ctx *c = p->c;
     int st = slot_check(c, first_slot, n_frames); if (st) return st;
     if ((uint64_t)p->frames + n_frames > p->capacity) return fail(c, GR_E_INVALID_ARG, "rmsd panel: append beyond the panel's capacity");
     if (p->epoch != c->epoch) {           // masses or groups changed: the weights must still be the context's masses of these atoms
-        for (uint32_t k = 0; k < p->n; ++k) if (memcmp(&c->masses_host[p->atoms[k]], &p->w_host[k], sizeof(float)) != 0)
-            return fail(c, GR_E_INVALID_ARG, "rmsd panel: the masses of its atoms have changed since it was created", p->atoms[k]);
+        for (uint32_t k = 0; k < p->n; ++k) if (memcmp(&c->masses_host[p->snap.atoms[k]], &p->w_host[k], sizeof(float)) != 0)
+            return fail(c, GR_E_INVALID_ARG, "rmsd panel: the masses of its atoms have changed since it was created", p->snap.atoms[k]);
         p->epoch = c->epoch;
     }
     (void)hipSetDevice(c->device);
-    const GrSel sel = rp_sel(p);
+    const GrSel sel = p->snap.sel;
     std::vector<int> stat(n_frames, GR_OK);
     grb::FirstError<gr_ctx> fe;
     for (const auto [b0, nb, s0] : grb::Segments{ first_slot, n_frames }) {
@@ -218,7 +211,7 @@ int rp_append(gr_rmsd_panel *p, uint32_t first_slot, uint32_t n_frames, int *sta
         st = states_from_prechecks(c, pre); if (st) return st;
         if (pre.any_ok) { st = pbc_center_stages(c, s0, nb, sel, 1); if (st) return st; }
         const size_t at = (size_t)p->frames + b0;
-        k_rp_pack<<<dim3(nb), dim3(GR_WG), 0, c->stream>>>(c->frames, c->frame_stride, s0, p->atoms_dev.get(), p->w_dev.get(), p->n, p->n_pad, c->boxes_dev, c->state_dev,
+        k_rp_pack<<<dim3(nb), dim3(GR_WG), 0, c->stream>>>(c->frames, c->frame_stride, s0, p->snap.atoms_dev.get(), p->w_dev.get(), p->n, p->n_pad, c->boxes_dev, c->state_dev,
                                                           p->x.get() + at * 3u * p->n_pad, p->G.get() + at, p->ok_dev.get() + at);
         HIPCHK(c, hipGetLastError());
         st = fetch_states(c, nb); if (st) return st;
@@ -268,21 +261,20 @@ gr_rmsd_panel *gr_rmsd_panel_create(gr_ctx *c, const char *group, uint32_t capac
     if (capacity_frames == 0 || capacity_frames > GR_RP_MAX_FRAMES) { *status = fail(c, GR_E_INVALID_ARG, "rmsd panel: capacity of 1 .. 2^20 frames"); return nullptr; }
     std::unique_ptr<gr_rmsd_panel> p(new gr_rmsd_panel());
     p->c = c; p->group = group; p->capacity = capacity_frames; p->epoch = c->epoch;
-    p->atoms = hb_group_atoms(*g);
-    p->n = (uint32_t)p->atoms.size();
+    std::vector<uint32_t> atoms = hb_group_atoms(*g);
+    p->n = (uint32_t)atoms.size();
     p->n_pad = (p->n + GR_RP_KSTEP - 1u) & ~(GR_RP_KSTEP - 1u);
     p->w_host.assign(p->n_pad, 0.0f);
     for (uint32_t k = 0; k < p->n; ++k) {
-        const float m = c->masses_host[p->atoms[k]];
-        if (m != m) { *status = fail(c, GR_E_NO_MASS, "atom has no mass", p->atoms[k]); return nullptr; }
+        const float m = c->masses_host[atoms[k]];
+        if (m != m) { *status = fail(c, GR_E_NO_MASS, "atom has no mass", atoms[k]); return nullptr; }
         p->w_host[k] = m; p->W += (double)m;
     }
     (void)hipSetDevice(c->device);
-    bool ok = p->atoms_dev.reserve(p->n, grbuf::exact) == hipSuccess && p->w_dev.reserve(p->n_pad, grbuf::exact) == hipSuccess &&
+    bool ok = p->snap.build(c, std::move(atoms), true) && p->w_dev.reserve(p->n_pad, grbuf::exact) == hipSuccess &&
               p->x.reserve((size_t)capacity_frames * 3u * p->n_pad, grbuf::exact) == hipSuccess && p->G.reserve(capacity_frames, grbuf::exact) == hipSuccess &&
               p->ok_dev.reserve(capacity_frames, grbuf::exact) == hipSuccess;
-    ok = ok && hipMemcpy(p->atoms_dev.get(), p->atoms.data(), 4 * (size_t)p->n, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(p->w_dev.get(), p->w_host.data(), 4 * (size_t)p->n_pad, hipMemcpyHostToDevice) == hipSuccess;
+    ok = ok && hipMemcpy(p->w_dev.get(), p->w_host.data(), 4 * (size_t)p->n_pad, hipMemcpyHostToDevice) == hipSuccess;
     if (!ok) {
         (void)hipGetLastError();
         *status = fail(c, GR_E_HIP, "rmsd panel: device allocation failed");
@@ -293,12 +285,7 @@ gr_rmsd_panel *gr_rmsd_panel_create(gr_ctx *c, const char *group, uint32_t capac
     return p.release();
 } catch (...) { if (status) *status = gr_abi_guard(); return nullptr; }
 
-void gr_rmsd_panel_destroy(gr_rmsd_panel *p) try {
-    if (!p) return;
-    (void)hipSetDevice(p->c->device);
-    (void)hipStreamSynchronize(p->c->stream);
-    delete p;                                              // (frees the grow-only buffers)
-} catch (...) { }
+void gr_rmsd_panel_destroy(gr_rmsd_panel *p) try { gr_object_destroy(p); } catch (...) { }
 
 int gr_rmsd_panel_append_batch(gr_rmsd_panel *p, uint32_t first_slot, uint32_t n_frames, int *status_out) try {
     if (!p) return GR_E_INVALID_ARG;

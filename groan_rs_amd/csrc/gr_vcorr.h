@@ -21,20 +21,15 @@
 //   X2 entries:              p = u_a * u_b, then SQRT2_F * p for a != b; SQRT2_F = (float)M_SQRT2
 // A FAILED frame (with PBC a frame without a usable box -- the box checks come first; a frame in which an atom named by any pair has
 // no position: GR_E_NO_POSITION and the lowest such atom) still takes a time index: its rows are zeros, its ok 0, it enters no pair.
-//   k_fl_check    (gr_fluct.h, unchanged; index-list form over the UNIQUE atoms the pairs name) the lowest atom without position, per frame
+//   k_fl_check    (gr_series.h; index-list form over the UNIQUE atoms the pairs name) the lowest atom without position, per frame
 //   k_vc_walk     <PBC, UNIT>: k_msd_walk's walk.  A lane owns ONE vector for the launch: it loads its two atom indices once (the table
 //                 is uint32 [2][n_pad], a wave's index loads are contiguous), turns them into six byte offsets and takes the segment's
 //                 frames in ascending order with the loads of GR_VC_AHEAD frames in flight (buffer loads, no load under a condition: a
 //                 frame beyond the segment is a resource of zero records, a pad an offset beyond every slot).  Consecutive lanes hold
 //                 consecutive vectors: every component of every frame is one contiguous store per wave.  Lane 0 of workgroup 0 writes ok.
-//   k_vc_gram     G = X X^T on v_mfma_f64_16x16x4_f64 in k_msd_gram's shape: the 64 x 64 blocks of frame pairs with block-row <=
-//                 block-column that touch the band, wave (wr, wc) owns a 32 x 32 quarter, the contraction runs over the K = 3 n_pad or
-//                 6 n_pad values of a row in trips of GR_MSD_TRIP, ascending, GR_MSD_AHEAD trips in flight (K / GR_MSD_TRIP = 4 C n_pad / 64
-//                 with C = 3 or 6 is always a multiple of GR_MSD_AHEAD = 3: the loop has no tail).  Every entry is ONE chain of ONE wave.
-//                 Unlike MSD the block's value is G itself and the diagonal t = t' is a valid pair (lag 0).  Valid entries (ok on both
-//                 sides, t <= t', t' - t <= max_lag) go to LDS and 127 lanes add one diagonal each, rows ascending.  blockIdx.y is the
-//                 panel: one launch serves both.
-//   k_msd_lags    (gr_msd.h, unchanged) one lane per lag: the partials of that lag in ascending block-row order
+//   k_band_gram<false>, k_band_lags   (gr_band.h, shared with MSD) the band product of the kept panels, K = 3 n_pad or 6 n_pad values
+//                 per row; blockIdx.y is the panel, one launch serves both.  Unlike MSD the block's value is G itself and the
+//                 diagonal t = t' is a valid pair (lag 0).
 //   k_vc_each     the curve of EVERY vector: the band closed per vector contracts 3 or 6 values only, so it is a direct VALU kernel.  A
 //                 wave owns 64 consecutive vectors and one lag; every (vector, lag) is ONE sequential f64 chain, frames ascending, within a
 //                 frame the components in panel order, each term fma((double)a, (double)b, s) -- the product of two f32 is exact in
@@ -45,8 +40,8 @@
 // CAPS: capacity x (3 + 6) x n_pad x 4 B over the kept panels <= GR_MSD_MAX_PANEL_BYTES; V x lags x 8 B of gr_vcorr_compute_each's
 // output per curve <= GR_VCORR_MAX_EACH_BYTES.
 #pragma once
-#include "gr_msd.h"
-#include "gr_internals.h"
+#include "gr_band.h"
+#include "gr_series.h"
 
 #if defined(__HIPCC__)
 
@@ -59,22 +54,21 @@
 struct gr_vcorr {
     gr_ctx *c = nullptr;
     uint32_t flags = 0, V = 0, n_pad = 0, capacity = 0;
-    std::vector<uint32_t> pairs;          // [V][2], the caller's order
-    std::vector<uint32_t> uniq;           // the atoms the pairs name, ascending, each once
-    GrSel sel = {};                       // ... as an index list for k_fl_check
-    grbuf::Dev<uint32_t> table_dev, uniq_dev, verdict_dev, ok_dev;       // [2][n_pad], [unique], [GR_MAX_BATCH + 2 AHEAD], [capacity]
-    grbuf::Pinned<uint32_t> verdict_host;
+    GrTuples tab;                         // the pairs, the atoms they name, the device table [2][n_pad]
+    GrVerdicts verdicts;
+    grbuf::Dev<uint32_t> ok_dev;          // [capacity]
     grbuf::Dev<float> X1, X2;             // [capacity][3][n_pad], [capacity][6][n_pad]; a panel that is not kept is empty
-    grbuf::Dev<double> part, sums, each;  // compute: [panels][blocks][GR_MSD_DIAGS], [panels][lags]; compute_each: [V][lags]
+    GrBandWork band;                      // compute
+    grbuf::Dev<double> each;              // compute_each: [V][lags]
     std::vector<uint8_t> ok_host;         // [frames]
     uint32_t frames = 0;                  // time indices taken
     uint64_t n_good = 0;
     bool computed = false;
     std::vector<double> sum_host[2];      // [lags] of the last compute, per panel
     std::vector<uint64_t> pairs_host;
-    uint32_t walk_groups = 0, gram_groups = 0, each_groups = 0;          // gr_vcorr_set_launch; 0: the default
-    uint32_t last_walk = 0, last_gram = 0, last_each = 0, last_lags = 0;
-    uint64_t launches = 0, blocks = 0;
+    uint32_t walk_groups = 0, each_groups = 0;        // gr_vcorr_set_launch; 0: the default
+    uint32_t last_walk = 0, last_each = 0, last_lags = 0;
+    uint64_t launches = 0;
 };
 
 namespace {
@@ -190,98 +184,6 @@ vc_walk_t vc_walk_kernel(uint32_t flags) {
     return unit ? k_vc_walk<false, true> : k_vc_walk<false, false>;
 }
 
-// block t of the band of panel blockIdx.y -> part[blockIdx.y][t][GR_MSD_DIAGS]; T frames, Ka / Kb values per row of panel 0 / 1, nblk block
-// rows, W = the farthest block column of a row
-__global__ __launch_bounds__(256) void k_vc_gram(const float *__restrict__ Xa, uint32_t Ka, const float *__restrict__ Xb, uint32_t Kb, const uint32_t *__restrict__ ok,
-                                                 uint32_t T, uint32_t nblk, uint32_t W, uint32_t nblocks, uint32_t max_lag, double *__restrict__ part) {
-    __shared__ double D[GR_MSD_BLOCK * GR_MSD_LD];
-    const float *__restrict__ X = blockIdx.y ? Xb : Xa;
-    const uint32_t K = blockIdx.y ? Kb : Ka;
-    part += (size_t)blockIdx.y * nblocks * GR_MSD_DIAGS;
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, m = lane & 15u, kg = lane >> 4;
-    const uint32_t wr = wave >> 1, wc = wave & 1u;
-    const uint32_t trips = K / GR_MSD_TRIP;                // a multiple of GR_MSD_AHEAD (see above)
-    const uint32_t r0 = nblk - W;
-    for (uint32_t t = blockIdx.x; t < nblocks; t += gridDim.x) {
-        uint32_t bi, db;
-        if (t < r0 * (W + 1u)) { bi = t / (W + 1u); db = t % (W + 1u); }
-        else {
-            uint32_t rem = t - r0 * (W + 1u);
-            bi = r0;
-            while (rem >= nblk - bi) { rem -= nblk - bi; ++bi; }
-            db = rem;
-        }
-        const uint32_t bj = bi + db;
-        gr_msd_d4 acc[2][2];
-#pragma unroll
-        for (uint32_t a = 0; a < 2u; ++a)
-#pragma unroll
-            for (uint32_t b = 0; b < 2u; ++b) acc[a][b] = (gr_msd_d4){ 0.0, 0.0, 0.0, 0.0 };
-        // (the quarter below the diagonal of a diagonal block holds no valid pair: its wave waits)
-        if (!(bi == bj && wr > wc)) {
-            // operand rows of this lane: tile a of A holds frames 64 bi + 32 wr + 16 a + m, tile b of B frames 64 bj + 32 wc + 16 b + m; a frame
-            // beyond the panel's last is read as the last (never closed)
-            const float *pa[2], *pb[2];
-#pragma unroll
-            for (uint32_t a = 0; a < 2u; ++a) {
-                pa[a] = X + (size_t)min(GR_MSD_BLOCK * bi + 32u * wr + 16u * a + m, T - 1u) * K + 4u * kg;
-                pb[a] = X + (size_t)min(GR_MSD_BLOCK * bj + 32u * wc + 16u * a + m, T - 1u) * K + 4u * kg;
-            }
-            // the operands of GR_MSD_AHEAD trips are in flight (behind the last trip: the last trip's again, never used); the MFMAs keep
-            // the ascending order of the trips
-            float4 a4[GR_MSD_AHEAD][2], b4[GR_MSD_AHEAD][2];
-#pragma unroll
-            for (uint32_t p = 0; p < GR_MSD_AHEAD; ++p) {
-                const size_t at = (size_t)min(p, trips - 1u) * GR_MSD_TRIP;
-#pragma unroll
-                for (uint32_t a = 0; a < 2u; ++a) { a4[p][a] = *reinterpret_cast<const float4 *>(pa[a] + at); b4[p][a] = *reinterpret_cast<const float4 *>(pb[a] + at); }
-            }
-            for (uint32_t g0 = 0; g0 < trips; g0 += GR_MSD_AHEAD) {
-#pragma unroll
-                for (uint32_t p = 0; p < GR_MSD_AHEAD; ++p) {
-                    const uint32_t g = g0 + p;
-                    if (g >= trips) break;                          // (never taken, see `trips`; without it the accumulators move between AGPRs and VGPRs every turn)
-                    const float av[2][4] = { { a4[p][0].x, a4[p][0].y, a4[p][0].z, a4[p][0].w }, { a4[p][1].x, a4[p][1].y, a4[p][1].z, a4[p][1].w } };
-                    const float bv[2][4] = { { b4[p][0].x, b4[p][0].y, b4[p][0].z, b4[p][0].w }, { b4[p][1].x, b4[p][1].y, b4[p][1].z, b4[p][1].w } };
-                    const size_t next = (size_t)min(g + GR_MSD_AHEAD, trips - 1u) * GR_MSD_TRIP;
-#pragma unroll
-                    for (uint32_t a = 0; a < 2u; ++a) { a4[p][a] = *reinterpret_cast<const float4 *>(pa[a] + next); b4[p][a] = *reinterpret_cast<const float4 *>(pb[a] + next); }
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-#pragma unroll
-                        for (int a = 0; a < 2; ++a)
-#pragma unroll
-                            for (int b = 0; b < 2; ++b) acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64((double)av[a][j], (double)bv[b][j], acc[a][b], 0, 0, 0);
-                }
-            }
-        }
-        // C/D map of the f64 form: lane holds column lane & 15, rows (lane >> 4) + 4 p of its tile
-#pragma unroll
-        for (uint32_t a = 0; a < 2u; ++a)
-#pragma unroll
-            for (uint32_t b = 0; b < 2u; ++b) {
-                const uint32_t j = 32u * wc + 16u * b + m, gj = GR_MSD_BLOCK * bj + j, cj = min(gj, T - 1u);
-                const bool okj = gj < T && ok[cj] != 0u;
-#pragma unroll
-                for (uint32_t p = 0; p < 4u; ++p) {
-                    const uint32_t i = 32u * wr + 16u * a + kg + 4u * p, gi = GR_MSD_BLOCK * bi + i, ci = min(gi, T - 1u);
-                    const bool valid = okj && gi <= gj && gj - gi <= max_lag && ok[ci] != 0u;
-                    D[i * GR_MSD_LD + j] = valid ? acc[a][b][p] : 0.0;
-                }
-            }
-        __syncthreads();
-        if (threadIdx.x < GR_MSD_DIAGS) {
-            // diagonal j - i = threadIdx.x - 63 of the block, rows ascending
-            const uint32_t dl = threadIdx.x;
-            const uint32_t i0 = dl < GR_MSD_BLOCK - 1u ? GR_MSD_BLOCK - 1u - dl : 0u, i1 = dl > GR_MSD_BLOCK - 1u ? GR_MSD_DIAGS - dl : GR_MSD_BLOCK;
-            double s = 0.0;
-            for (uint32_t i = i0; i < i1; ++i) s += D[i * GR_MSD_LD + i + dl - (GR_MSD_BLOCK - 1u)];
-            part[(size_t)t * GR_MSD_DIAGS + dl] = s;
-        }
-        __syncthreads();
-    }
-}
-
 // out[k][tau] = the chain of vector k and lag tau over a panel of C components; a wave takes 64 consecutive vectors and one lag
 template <int C>
 __global__ __launch_bounds__(256) void k_vc_each(const float *__restrict__ X, uint32_t npad, uint32_t V, const uint32_t *__restrict__ ok, uint32_t T, uint32_t lags,
@@ -325,34 +227,30 @@ int vc_append(gr_vcorr *v, uint32_t first_slot, uint32_t n_frames, int *status_o
     const uint32_t slot_bytes = (uint32_t)(c->frame_stride * sizeof(float));
     const vc_walk_t kernel = vc_walk_kernel(v->flags);
     const size_t np = v->n_pad;
-    uint32_t *vh = v->verdict_host.get(), *vd = v->verdict_dev.get();
+    GrVerdicts &R = v->verdicts;
+    const uint32_t *vd = R.dev.get();
     v->computed = false;
     grb::FirstError<gr_ctx> fe;
     for (const auto [b0, nb, s0] : grb::Segments{ first_slot, n_frames }) {
         const grb::Prechecks pre(c, { b0, nb, s0 }, box_checks(c, pbc));
-        for (uint32_t k = 0; k < nb; ++k) vh[k] = pre.ok(k) ? GR_NOIDX : GR_FL_SKIP;
-        for (uint32_t k = nb; k < nb + 2u * GR_VC_AHEAD; ++k) vh[k] = GR_FL_SKIP;
         {
             // (launched even when every frame failed its checks: the rows of failed frames are written as zeros)
             SlotUse use(c, s0, nb);
-            HIPCHK(c, hipMemcpyAsync(vd, vh, (nb + 2u * GR_VC_AHEAD) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-            // launch geometry: one wave per 64 vectors of the padded list, 256 atoms per workgroup of the check; gr_vcorr_set_launch
-            // replaces the number of the walk's ranges
+            st = R.begin(c, pre, nb); if (st) return st;
+            // launch geometry: one wave per 64 vectors of the padded list; gr_vcorr_set_launch replaces the number of the walk's ranges
             const uint32_t wx = std::min<uint32_t>(v->walk_groups ? v->walk_groups : v->n_pad / GR_VC_WG, GR_VC_MAX_WALK);
-            const uint32_t check = std::min<uint32_t>(((uint32_t)v->uniq.size() + 255u) / 256u, GR_FL_CHECK_WGS);
             const size_t at = (size_t)v->frames + b0;
             float *r1 = (v->flags & GR_VCORR_P1) ? v->X1.get() + at * 3u * np : nullptr;
             float *r2 = (v->flags & GR_VCORR_P2) ? v->X2.get() + at * 6u * np : nullptr;
-            if (pre.any_ok) k_fl_check<<<dim3(check, nb), dim3(256), 0, c->stream>>>(c->frames, c->frame_stride, s0, v->sel, 1, vd);
-            kernel<<<dim3(wx), dim3(GR_VC_WG), 0, c->stream>>>(c->frames, c->frame_stride, slot_bytes, s0, nb, v->table_dev.get(), v->V, v->n_pad, c->boxes_dev, vd, r1, r2,
+            if (pre.any_ok) R.check(c, v->tab.uniq, s0, nb);
+            kernel<<<dim3(wx), dim3(GR_VC_WG), 0, c->stream>>>(c->frames, c->frame_stride, slot_bytes, s0, nb, v->tab.table_dev.get(), v->V, v->n_pad, c->boxes_dev, vd, r1, r2,
                                                                v->ok_dev.get() + at);
             HIPCHK(c, hipGetLastError());
             ++v->launches; v->last_walk = wx;
-            HIPCHK(c, hipMemcpyAsync(vh, vd, nb * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
+            st = R.end(c, nb); if (st) return st;
         }
         for (uint32_t k = 0; k < nb; ++k) {
-            const int s = grb::close_frame(c, fe, pre, k, status_out, [&] { return ic_judge(c, vh[k]); });
+            const int s = grb::close_frame(c, fe, pre, k, status_out, [&] { return R.judge(c, k); });
             v->ok_host.push_back(s == GR_OK ? 1 : 0);
             if (s == GR_OK) ++v->n_good;
         }
@@ -361,53 +259,27 @@ int vc_append(gr_vcorr *v, uint32_t first_slot, uint32_t n_frames, int *status_o
     return fe.finish(c);
 }
 
-// pairs[tau] = the t with ok[t] and ok[t + tau]: integer work on the host
-void vc_pairs(const gr_vcorr *v, uint32_t lags, std::vector<uint64_t> &out) {
-    out.assign(lags, 0u);
-    const uint8_t *okh = v->ok_host.data();
-    const uint32_t T = v->frames;
-    for (uint32_t tau = 0; tau < lags; ++tau) {
-        uint64_t n = 0;
-        for (uint32_t t = 0; t + tau < T; ++t) n += (uint64_t)(okh[t] & okh[t + tau]);
-        out[tau] = n;
-    }
-}
-
 int vc_compute(gr_vcorr *v, uint32_t max_lag) {
     gr_ctx *c = v->c;
     int st = busy_check(c); if (st) return st;
     if (v->frames == 0) return fail(c, GR_E_INVALID_ARG, "vcorr: no frame has been appended");
     (void)hipSetDevice(c->device);
-    const uint32_t T = v->frames;
-    max_lag = std::min(max_lag, T - 1u);                   // (a lag beyond the last frame has no pair: clamped)
-    const uint32_t lags = max_lag + 1u;
-    const uint32_t nblk = (T + GR_MSD_BLOCK - 1u) / GR_MSD_BLOCK;
-    const uint32_t W = std::min(nblk - 1u, (max_lag + GR_MSD_BLOCK - 1u) / GR_MSD_BLOCK);
-    const uint64_t nblocks = (uint64_t)(nblk - W) * (W + 1u) + (uint64_t)W * (W + 1u) / 2u;
-    if (nblocks > 0x7fffffffull) return fail(c, GR_E_INVALID_ARG, "vcorr: too many blocks of frame pairs for one compute");
     const uint32_t ranks = vc_ranks(v);
-    if (v->part.reserve((size_t)ranks * nblocks * GR_MSD_DIAGS, grbuf::exact) != hipSuccess || v->sums.reserve((size_t)ranks * lags, grbuf::exact) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(c, GR_E_HIP, "vcorr: device allocation failed");
-    }
+    grband::Geometry g;
+    st = band_reserve(c, "vcorr", v->band, v->frames, max_lag, ranks, g); if (st) return st;
+    const uint32_t lags = g.lags;
     // the kept panels in rank order: panel 0 of the launch is X1 when it is kept
     const bool p1 = (v->flags & GR_VCORR_P1) != 0u;
-    const float *Xa = p1 ? v->X1.get() : v->X2.get(), *Xb = v->X2.get();
-    const uint32_t Ka = (p1 ? 3u : 6u) * v->n_pad, Kb = 6u * v->n_pad;
-    uint32_t grid = (uint32_t)nblocks;
-    if (v->gram_groups && v->gram_groups < grid) grid = v->gram_groups;
-    k_vc_gram<<<dim3(grid, ranks), dim3(256), 0, c->stream>>>(Xa, Ka, Xb, Kb, v->ok_dev.get(), T, nblk, W, (uint32_t)nblocks, max_lag, v->part.get());
-    for (uint32_t r = 0; r < ranks; ++r)
-        k_msd_lags<<<dim3((lags + 255u) / 256u), dim3(256), 0, c->stream>>>(v->part.get() + (size_t)r * nblocks * GR_MSD_DIAGS, nblk, W, lags, v->sums.get() + (size_t)r * lags);
-    HIPCHK(c, hipGetLastError());
-    ++v->launches; v->last_gram = grid; v->blocks = nblocks;
+    st = band_launch<false>(c, v->band, g, ranks, p1 ? v->X1.get() : v->X2.get(), (p1 ? 3u : 6u) * v->n_pad, v->X2.get(), 6u * v->n_pad, nullptr, v->ok_dev.get(), v->frames);
+    if (st) return st;
+    ++v->launches;
     v->sum_host[0].clear(); v->sum_host[1].clear();
     for (uint32_t r = 0; r < ranks; ++r) {
         std::vector<double> &dst = v->sum_host[(r == 0 && p1) ? 0 : 1];
         dst.assign(lags, 0.0);
-        HIPCHK(c, hipMemcpyAsync(dst.data(), v->sums.get() + (size_t)r * lags, lags * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(dst.data(), v->band.sums.get() + (size_t)r * lags, lags * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     }
-    vc_pairs(v, lags, v->pairs_host);                      // meanwhile
+    grband::pair_counts(v->ok_host.data(), v->frames, lags, v->pairs_host);      // meanwhile
     HIPCHK(c, hipStreamSynchronize(c->stream));
     v->computed = true; v->last_lags = lags;
     return GR_OK;
@@ -431,7 +303,7 @@ int vc_compute_each(gr_vcorr *v, uint32_t max_lag, double *c1, double *c2) {
         return fail(c, GR_E_HIP, "vcorr: device allocation failed");
     }
     std::vector<uint64_t> pairs;
-    vc_pairs(v, lags, pairs);
+    grband::pair_counts(v->ok_host.data(), T, lags, pairs);
     const uint64_t units = (uint64_t)(v->n_pad / 64u) * lags;
     uint32_t grid = (uint32_t)std::min<uint64_t>((units + 3u) / 4u, GR_VC_MAX_EACH);
     if (v->each_groups && v->each_groups < grid) grid = v->each_groups;
@@ -483,50 +355,22 @@ gr_vcorr *gr_vcorr_create(gr_ctx *c, const uint64_t *atoms, uint64_t n_vectors, 
         *status = fail(c, GR_E_INVALID_ARG, "vcorr: the panels (capacity x 3 and x 6 x n_pad x 4 B) exceed GR_MSD_MAX_PANEL_BYTES = " + std::to_string((unsigned long long)GR_MSD_MAX_PANEL_BYTES));
         return nullptr;
     }
-    v->pairs.resize((size_t)v->V * 2u);
-    for (uint64_t t = 0; t < n_vectors; ++t) {
-        for (uint32_t a = 0; a < 2u; ++a) {
-            const uint64_t i = atoms[t * 2u + a];
-            if (i >= c->n) { *status = fail(c, GR_E_OUT_OF_RANGE, "vcorr: atom index out of range", i); return nullptr; }
-            v->pairs[t * 2u + a] = (uint32_t)i;
-        }
-        if (atoms[t * 2u] == atoms[t * 2u + 1u]) { *status = fail(c, GR_E_INVALID_ARG, "vcorr: a pair names one atom twice", t); return nullptr; }
-    }
-    v->uniq = v->pairs;
-    std::sort(v->uniq.begin(), v->uniq.end());
-    v->uniq.erase(std::unique(v->uniq.begin(), v->uniq.end()), v->uniq.end());
-    std::vector<uint32_t> table(2u * (size_t)v->n_pad, 0u);
-    for (uint32_t t = 0; t < v->V; ++t)
-        for (uint32_t a = 0; a < 2u; ++a) table[(size_t)a * v->n_pad + t] = v->pairs[(size_t)t * 2u + a];
-    (void)hipSetDevice(c->device);
+    *status = v->tab.build(c, "vcorr", "a pair names one atom twice", atoms, n_vectors, 2u, v->n_pad); if (*status) return nullptr;
     const size_t np = v->n_pad;
-    bool ok = v->table_dev.reserve(table.size(), grbuf::exact) == hipSuccess && v->uniq_dev.reserve(v->uniq.size(), grbuf::exact) == hipSuccess &&
-              v->ok_dev.reserve(capacity_frames, grbuf::exact) == hipSuccess &&
-              v->verdict_dev.reserve(GR_MAX_BATCH + 2u * GR_VC_AHEAD, grbuf::exact) == hipSuccess &&
-              v->verdict_host.reserve(GR_MAX_BATCH + 2u * GR_VC_AHEAD, grbuf::exact) == hipSuccess;
+    bool ok = v->verdicts.reserve(2u * GR_VC_AHEAD) && v->ok_dev.reserve(capacity_frames, grbuf::exact) == hipSuccess;
     if (flags & GR_VCORR_P1) ok = ok && v->X1.reserve((size_t)capacity_frames * 3u * np, grbuf::exact) == hipSuccess;
     if (flags & GR_VCORR_P2) ok = ok && v->X2.reserve((size_t)capacity_frames * 6u * np, grbuf::exact) == hipSuccess;
-    ok = ok && hipMemcpy(v->table_dev.get(), table.data(), 4 * table.size(), hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(v->uniq_dev.get(), v->uniq.data(), 4 * v->uniq.size(), hipMemcpyHostToDevice) == hipSuccess;
     ok = ok && vc_zero(v.get()) == GR_OK && hipStreamSynchronize(c->stream) == hipSuccess;
     if (!ok) {
         (void)hipGetLastError();
         *status = fail(c, GR_E_HIP, "vcorr: device allocation failed");
         return nullptr;
     }
-    GrSel &s = v->sel;
-    s.n = (uint32_t)v->uniq.size(); s.contiguous = 0u; s.start = v->uniq.front(); s.g0 = s.start >> 8; s.idx = v->uniq_dev.get();
-    s.masked = 0u; s.span = v->uniq.back() - s.start + 1u; s.mask = nullptr;
     *status = GR_OK;
     return v.release();
 } catch (...) { if (status) *status = gr_abi_guard(); return nullptr; }
 
-void gr_vcorr_destroy(gr_vcorr *v) try {
-    if (!v) return;
-    (void)hipSetDevice(v->c->device);
-    (void)hipStreamSynchronize(v->c->stream);
-    delete v;                                              // (frees the grow-only buffers)
-} catch (...) { }
+void gr_vcorr_destroy(gr_vcorr *v) try { gr_object_destroy(v); } catch (...) { }
 
 uint64_t gr_vcorr_count(const gr_vcorr *v) { return v ? v->V : 0u; }
 uint64_t gr_vcorr_frames(const gr_vcorr *v) { return v ? v->frames : 0u; }
@@ -599,7 +443,7 @@ int gr_vcorr_read_vectors(gr_vcorr *v, uint32_t t0, uint32_t nt, float *out) try
 
 int gr_vcorr_set_launch(gr_vcorr *v, uint32_t walk_groups, uint32_t gram_groups, uint32_t each_groups) try {
     if (!v) return GR_E_INVALID_ARG;
-    v->walk_groups = walk_groups; v->gram_groups = gram_groups; v->each_groups = each_groups;
+    v->walk_groups = walk_groups; v->band.gram_groups = gram_groups; v->each_groups = each_groups;
     return GR_OK;
 } catch (...) { return gr_abi_guard(); }
 
@@ -610,9 +454,9 @@ int gr_vcorr_stat(const gr_vcorr *v, int key, uint64_t *value) try {
     case GR_VCORR_STAT_N_PAD: *value = v->n_pad; return GR_OK;
     case GR_VCORR_STAT_LAGS: *value = v->computed ? v->last_lags : 0u; return GR_OK;
     case GR_VCORR_STAT_LAST_WALK_GROUPS: *value = v->last_walk; return GR_OK;
-    case GR_VCORR_STAT_LAST_GRAM_GROUPS: *value = v->last_gram; return GR_OK;
+    case GR_VCORR_STAT_LAST_GRAM_GROUPS: *value = v->band.last_gram; return GR_OK;
     case GR_VCORR_STAT_LAST_EACH_GROUPS: *value = v->last_each; return GR_OK;
-    case GR_VCORR_STAT_LAST_BLOCKS: *value = v->blocks; return GR_OK;
+    case GR_VCORR_STAT_LAST_BLOCKS: *value = v->band.blocks; return GR_OK;
     case GR_VCORR_STAT_COUNTED: *value = v->n_good; return GR_OK;
     default: return GR_E_INVALID_ARG;
     }

@@ -6,12 +6,15 @@ for bit, the curve under the derived bound of tests/test_gpu_msd.py, and itself 
                 an object whose capacity is exactly that
   the segment   one append of 1025 frames of a 33-atom system, across the 1024-frame cut of a batched call
   max_lag       0, 1, 63, 64, 65, frames - 1 and beyond: each curve a prefix of the full one, bit for bit
+  one atom      65 frames (two block rows, the second with one live frame), one of them failed, max_lag 3 and 64: the curve bit for bit in
+                the order of the band's sums (tests/band_ref.py) -- the product's two-panel launch with its one panel
   clear         followed by re-use"""
 import functools
 
 import numpy as np
 import pytest
 
+import band_ref as B
 import msd_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -153,3 +156,30 @@ def test_clear_and_reuse(G, world):
         a.append(0, 40); b.append(0, 40)                                                   # the full capacity again, a new origin
         assert R.same_bits(a.displacements(0, 40), w.panel()[:40])
         assert a.msd()[0].tobytes() == b.msd()[0].tobytes() and a.from_origin().tobytes() == b.from_origin().tobytes()
+
+
+def test_one_atom_in_the_order_of_the_band(G):
+    frames, boxes = walk(6, 65, "ortho")[:2]
+    frames = [x.copy() for x in frames]
+    frames[62][4] = np.nan
+    s = make_system(G, frames, boxes)
+    s.group_create_from_ranges("one", [(4, 4)])
+    w = R.Walk(1)
+    st, bad = w.append(frames, boxes, np.arange(4, 5))
+    assert st.tolist() == [0] * 62 + [R.E_NO_POSITION, 0, 0]
+    with G.MSD(s, "one", 65) as m:
+        assert m.append(0, 65, raise_on_error=False).tolist() == st.tolist()
+        assert m.stat(G._lib.MSD_STAT_N_PAD) == 64 and m.stat(G._lib.MSD_STAT_COUNTED) == 64
+        d = m.displacements(0, 65)
+        assert R.same_bits(d, w.panel()) and not d[62].any() and d[64].any()
+        q = m.from_origin()                                                                 # one atom: the rows' squared norms themselves
+        assert np.isnan(q[62]) and not np.isnan(np.delete(q, 62)).any()
+        value = (q[:, None] + q[None, :]) - 2.0 * B.gram(d[:, 0, :])
+        for lag in (3, 64):
+            msd, pairs = within_bound(G, m, w.panel(), w.ok, lag)
+            assert pairs[0] == 64 and pairs[1] == 62 and m.stat(G._lib.MSD_STAT_LAST_BLOCKS) == 3 == m.stat(G._lib.MSD_STAT_LAST_GRAM_GROUPS)
+            want = B.band_sums(value, w.ok, lag, strict=True) / pairs.astype(np.float64)
+            print("max_lag %d: largest difference from the restated order %.3g" % (lag, np.abs(msd - want).max()))
+            assert R.same_bits(msd, want)
+        assert pairs[64] == 1
+    s.close()

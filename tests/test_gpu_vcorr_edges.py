@@ -8,12 +8,16 @@ bit for bit under another launch setting.
   the segment   one append of 1030 frames of 5 vectors, across the 1024-frame cut of a batched call, against pieces of 7
   failed frames at time index 0, 63, 64 and the last: a named atom without position, an atom no pair names (fails nothing), with a
                 minimum image a frame without a box; the pair counts are the host formula's, the rows zeros
+  one kept panel a P1-only and a P2-only object (panel 0 of the product's launch is X1 or X2, the grid one panel high) of ONE vector, 65 frames
+                (two block rows, the second with one live frame), one of them failed, max_lag 3 and 64: the curves bit for bit in the
+                order of the band's sums (tests/band_ref.py), and the bits of the object that keeps both panels
   the product's prefetch depth (3 trips) divides every trip count (12 or 24 per 64 vectors): there is no tail to leave"""
 import functools
 
 import numpy as np
 import pytest
 
+import band_ref as B
 import vcorr_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -300,3 +304,35 @@ def test_an_output_above_the_cap_is_refused(G, system):
         q = R.Panels(pairs[:70], unit=False)
         q.append(world()[0][:65])
         assert e2 is None and e1.shape == (V, 4) and R.same_bits(np.ascontiguousarray(e1[:70]), R.each(q.x1(), q.ok, 1, 3))
+
+
+@pytest.mark.parametrize("rank", [1, 2])
+def test_one_kept_panel_of_one_vector_in_the_order_of_the_band(G, rank):
+    frames, boxes, pairs, straddle = world(3, 65, "ortho")
+    frames = [x.copy() for x in frames]
+    pairs = pairs[1:2]                                                                      # the vector (2, 3)
+    frames[62][3] = np.nan
+    s = make_system(G, frames, boxes)
+    q = R.Panels(pairs)
+    st, bad = q.append(frames)
+    assert st.tolist() == [0] * 62 + [R.E_NO_POSITION, 0, 0] and bad[62] == 3
+    x1 = q.x1()
+    panel = x1 if rank == 1 else R.rank2(x1)
+    value = B.gram(panel[:, 0, :])
+    with G.VectorCorrelation(s, pairs, 65, rank=rank) as v, G.VectorCorrelation(s, pairs, 65) as both:
+        for x in (v, both):
+            assert x.append(0, 65, raise_on_error=False).tolist() == st.tolist()
+        assert v.stat(G._lib.VCORR_STAT_N_PAD) == 64 and v.stat(G._lib.VCORR_STAT_COUNTED) == 64
+        assert R.same_bits(both.vectors(0, 65), x1) and not x1[62].any()
+        for lag in (3, 64):
+            out = v.correlate(lag)
+            got, cnt = out[rank - 1], out[2]
+            assert out[2 - rank] is None and np.array_equal(cnt, R.pair_counts(q.ok, lag)) and cnt[0] == 64 and cnt[1] == 62
+            assert v.stat(G._lib.VCORR_STAT_LAST_BLOCKS) == 3 and v.stat(G._lib.VCORR_STAT_LAST_GRAM_GROUPS) == 3
+            want = R.close(B.band_sums(value, q.ok, lag, strict=False), cnt.astype(np.float64), rank)
+            print("rank %d, max_lag %d: largest difference from the restated order %.3g" % (rank, lag, np.abs(got - want).max()))
+            assert R.same_bits(got, want)
+            assert got.tobytes() == both.correlate(lag)[rank - 1].tobytes()
+            assert R.same_bits(v.correlate_each(lag)[rank - 1], R.each(panel, q.ok, rank, lag))
+        assert cnt[64] == 1
+    s.close()

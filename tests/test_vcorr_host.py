@@ -58,7 +58,7 @@ def test_header_section_is_mirrored_in_lib_hpp_and_rust():
                    "GR_MSD_MAX_PANEL_BYTES", "GR_VCORR_MAX_EACH_BYTES", "Out of scope"):
         assert phrase in flat, phrase
     src = open(os.path.join(ROOT, "groan_rs_amd", "csrc", "gr_vcorr.h")).read()
-    for phrase in ("THE RULE", "STILL", "GR_MSD_MAX_PANEL_BYTES", "GR_VCORR_MAX_EACH_BYTES", "k_msd_lags", "k_vc_gram", "k_vc_walk", "k_vc_each"):
+    for phrase in ("THE RULE", "STILL", "GR_MSD_MAX_PANEL_BYTES", "GR_VCORR_MAX_EACH_BYTES", "k_band_lags", "k_band_gram", "k_vc_walk", "k_vc_each"):
         assert phrase in src, phrase
     api = open(os.path.join(ROOT, "groan_rs_amd", "csrc", "gr_api.hip")).read()
     assert api.index('#include "gr_internals.h"') < api.index('#include "gr_vcorr.h"')

@@ -54,7 +54,7 @@ def main():
     for (i0, mangled), name in zip(starts, names):
         if ".amdhsa_kernel " + mangled not in "\n".join(lines[i0:i0 + 20000]) and not any(l.startswith("\t.amdhsa_kernel " + mangled) for l in lines):
             continue
-        short = re.sub(r"\(.*", "", name).replace("void ", "")
+        short = re.sub(r"\(.*", "", name.replace("(anonymous namespace)::", "")).replace("void ", "")
         if args.kernel and not any(k in short for k in args.kernel):
             continue
         end = next(j for j in range(i0, len(lines)) if lines[j].startswith(".Lfunc_end"))
@@ -99,10 +99,10 @@ def main():
     out.append("kernel resource usage and hot-loop instruction mix, gfx950 (hipcc -O3, ROCm 7.2; tools/isa_stats.py)")
     out.append("VALU / trip = v_* + v_pk_* instructions in the kernel's largest loop (all blocks inside it, rare-path blocks included)")
     out.append("")
-    out.append("%-58s %5s %5s %6s %7s %4s %7s | %5s %5s %5s %5s %5s" % ("kernel", "VGPR", "SGPR", "LDS B", "scratch", "occ", "code B", "valu", "pk", "salu", "vmem", "lds"))
+    out.append("%-58s %5s %5s %5s %6s %7s %4s %7s | %5s %5s %5s %5s %5s" % ("kernel", "VGPR", "AGPR", "SGPR", "LDS B", "scratch", "occ", "code B", "valu", "pk", "salu", "vmem", "lds"))
     for short, r, best in rows:
         mix = best[1] if best else {}
-        out.append("%-58s %5s %5s %6s %7s %4s %7s | %5d %5d %5d %5d %5d" % (short[:58], r["vgpr"], r["sgpr"], r["lds"], r["scratch"], r["occ"], r["code"],
+        out.append("%-58s %5s %5s %5s %6s %7s %4s %7s | %5d %5d %5d %5d %5d" % (short[:58], r["vgpr"], r["agpr"], r["sgpr"], r["lds"], r["scratch"], r["occ"], r["code"],
                                                                             mix.get("valu", 0) + mix.get("valu_pk", 0), mix.get("valu_pk", 0), mix.get("salu", 0), mix.get("vmem", 0), mix.get("lds", 0)))
     text = "\n".join(out) + "\n"
     sys.stdout.write(text)
