@@ -12,7 +12,7 @@ from .traj import (FrameAnalyze, FrameConvert, FrameConvertAnalyze, RMSDConverte
                    TrajAnalysisError, TrajConverter, TrajConverterAnalyzer, TrajReader)
 from .hbonds import HBOND_DTYPE, HBondAnalysis, HBondChain, HBondError
 from .gridmap import GridMap, GridMapError, TileGeometry
-from .segments import Segments
+from .segments import Gyration, Segments, shape_descriptors
 from .region import Region
 from .contacts import Contacts
 from .rmsd_matrix import RMSDPanel, rmsd_matrix
@@ -31,6 +31,6 @@ from .parallel import AbortedByOtherRank, Comm, ParallelTrajData, Pool, gather_p
 __all__ = [
     "AtomContainer", "AtomError", "AtomIterator", "DeviceError", "Dimension", "GroanError", "GroupError", "RMSDError", "RMSDPlan",
     "SimBoxError", "System", "pinned_array", "pinned_free", "FrameAnalyze", "FrameConvert", "FrameConvertAnalyze", "RMSDConverterAnalyzer",
-    "TrajAnalyzer", "TrajAnalysisError", "HBOND_DTYPE", "HBondAnalysis", "HBondChain", "HBondError", "GridMap", "GridMapError", "TileGeometry", "Segments", "Region", "Contacts", "RMSDPanel", "rmsd_matrix", "Fluctuations", "Covariance", "MSD", "Internals", "angles_from_bonds", "dihedrals_from_bonds", "VectorCorrelation", "TrajConverter", "TrajConverterAnalyzer", "TrajReader",
+    "TrajAnalyzer", "TrajAnalysisError", "HBOND_DTYPE", "HBondAnalysis", "HBondChain", "HBondError", "GridMap", "GridMapError", "TileGeometry", "Segments", "Gyration", "shape_descriptors", "Region", "Contacts", "RMSDPanel", "rmsd_matrix", "Fluctuations", "Covariance", "MSD", "Internals", "angles_from_bonds", "dihedrals_from_bonds", "VectorCorrelation", "TrajConverter", "TrajConverterAnalyzer", "TrajReader",
     "XtcError", "XtcFile", "XtcWriter", "ParseGroError", "ParseNdxError", "Structure", "read_ndx_groups", "system_from_gro", "system_read_ndx", "Cylinder", "Rectangular", "Shape", "Sphere", "TriangularPrism", "AbortedByOtherRank", "Comm", "Pool", "ParallelTrajData", "gather_per_frame", "interleave", "shard_frames", "traj_iter_map_reduce",
 ]

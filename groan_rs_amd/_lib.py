@@ -26,6 +26,7 @@ GM_WRAP, GM_FORCE_GLOBAL = 1, 2
 GM_STAT_LDS_LAUNCHES, GM_STAT_GLOBAL_LAUNCHES, GM_STAT_LDS_BUDGET = 1, 2, 3
 GM_STAT_LAST_RANGE_GROUPS, GM_STAT_LAST_FRAME_GROUPS, GM_STAT_LAST_CHECK_GROUPS = 4, 5, 6
 SEG_STAT_TEAM4, SEG_STAT_TEAM16, SEG_STAT_WAVE, SEG_STAT_WORKGROUP, SEG_STAT_LAST_LAUNCHES, SEG_STAT_LAST_LAUNCH_SETS = 1, 2, 3, 4, 5, 6
+SEG_STAT_LAST_PIECES = 7
 RG_STAT_LAST_LAUNCHES, RG_STAT_LAST_PIECES, RG_STAT_LAST_TOTAL, RG_STAT_CHUNK = 1, 2, 3, 4
 CT_STAT_LAST_LAUNCHES, CT_STAT_LAST_PIECES, CT_STAT_LAST_TOTAL, CT_STAT_TILE = 1, 2, 3, 4
 CT_STAT_LAST_RUNS, CT_STAT_LAST_CELLS, CT_STAT_LAST_RUN_CELLS_MIN, CT_STAT_LAST_RUN_CELLS_MAX, CT_STAT_LAST_WALK_GROUPS = 5, 6, 7, 8, 9
@@ -182,6 +183,10 @@ SIGNATURES = {
     "gr_segments_stat": (C.c_int, [C.c_void_p, C.c_int, c_u64p]),
     "gr_segments_center_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "gr_segments_center_batch_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_void_p), c_u64p, C.c_void_p]),
+    "gr_segments_gyration_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gr_segments_gyration_batch_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), c_u64p,
+                                                    C.c_void_p]),
+    "gr_segments_set_piece_frames": (C.c_int, [C.c_void_p, C.c_uint32]),
     "gr_region_create": (C.c_void_p, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, c_i32p]),
     "gr_region_destroy": (None, [C.c_void_p]),
     "gr_region_select_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -3731,6 +3731,7 @@ int gr_synth_uniform(gr_ctx *c, uint32_t slot, const float *box9, uint64_t seed)
 #include "gr_whole.h"    // bond topology, make_molecules_whole / make_group_whole: kernels and C ABI
 #include "gr_gridmap.h"  // GridMap: tile maps accumulated over batches of resident frames: geometry, kernels and C ABI
 #include "gr_segments.h" // Segments: per-residue / per-molecule centres of resident frames: partition, kernel and C ABI
+#include "gr_gyration.h" // Segments: gyration tensor, Rg and principal axes of every segment: closing arithmetic, kernels and C ABI
 #include "gr_region.h"   // Region: geometry selections over a block of resident frames: kernels, object and C ABI
 #include "gr_contacts.h" // Contacts: cut-off pair search over a block of resident frames: kernels, object and C ABI
 #include "gr_series.h"   // what the objects over batches of resident frames share: snapshot, tuple table, the round of verdicts (k_fl_check), destroy

@@ -196,6 +196,11 @@ struct gr_segments {
     unsigned long long *key_dev = nullptr, *key_host = nullptr;   // [GR_MAX_BATCH]: the frames' first errors
     uint32_t *ok_dev = nullptr, *ok_host = nullptr;               // [GR_MAX_BATCH]: the frame passed its host checks
     uint64_t last_launches = 0, last_sets = 0;
+    // gr_gyration.h: the device block of a piece of frames ([piece][M][10] moments, then [piece][M][12] axes from gyr_axes_at on)
+    grbuf::Dev<float> gyr;
+    size_t gyr_axes_at = 0;
+    uint32_t piece_frames = 0;                           // 0: by GR_GYR_BLOCK_BYTES
+    uint64_t last_pieces = 0;
 };
 
 namespace {
@@ -479,6 +484,7 @@ int gr_segments_stat(const gr_segments *S, int key, uint64_t *value) try {
         *value = S->P.class_count[key - GR_SEG_STAT_TEAM4]; return GR_OK;
     case GR_SEG_STAT_LAST_LAUNCHES: *value = S->last_launches; return GR_OK;
     case GR_SEG_STAT_LAST_LAUNCH_SETS: *value = S->last_sets; return GR_OK;
+    case GR_SEG_STAT_LAST_PIECES: *value = S->last_pieces; return GR_OK;
     default: return GR_E_INVALID_ARG;
     }
 } catch (...) { return gr_abi_guard(); }

@@ -2,7 +2,8 @@
 
 The reference's loop is `for part in group_split_by_resid(..) { group_get_com(part) }` (src/system/groups.rs:344-435, :514-558) or the
 same over `molecule_iter` (iterating.rs:238-245), once per frame.  Here the parts are one object (gr_segments_*): made once, then
-`centers` returns all of them for n_frames slots.  No arithmetic on atoms happens in Python.
+`centers` returns all of them for n_frames slots, and `gyration` their shape: radius of gyration, gyration tensor and principal axes
+(gmx gyrate / gmx principal for every part at once).  No arithmetic on atoms happens in Python.
 """
 import ctypes as C
 
@@ -11,6 +12,30 @@ import numpy as np
 from . import _lib
 from ._lib import OK, CENTER_ESTIMATE, CENTER_NAIVE, CENTER_PBC
 from .system import _ptr
+
+
+class Gyration:
+    """what Segments.gyration returns, as views of the call's two blocks (F frames, M segments):
+    center [F, M, 3] nm, rg [F, M] nm, tensor [F, M, 3, 3] nm^2 (symmetric), status [F]; with axes: eigenvalues [F, M, 3] nm^2
+    (descending) and axes [F, M, 3, 3] (rows v1, v2, v3), else both None.  `moments` [F, M, 10] and `raw_axes` [F, M, 12] are the blocks"""
+
+    def __init__(self, moments, raw_axes, status):
+        self.moments, self.raw_axes, self.status = moments, raw_axes, status
+        self.center, self.rg = moments[..., 0:3], moments[..., 3]
+        self.tensor = moments[..., [4, 7, 8, 7, 5, 9, 8, 9, 6]].reshape(moments.shape[:-1] + (3, 3))
+        self.eigenvalues = raw_axes[..., 0:3] if raw_axes is not None else None
+        self.axes = raw_axes[..., 3:12].reshape(raw_axes.shape[:-1] + (3, 3)) if raw_axes is not None else None
+
+
+def shape_descriptors(eigenvalues):
+    """eigenvalues [..., 3] of a gyration tensor (descending) -> (asphericity l1 - (l2 + l3) / 2, acylindricity l2 - l3, relative shape
+    anisotropy 1.5 sum l^2 / (sum l)^2 - 0.5, which is 0 where sum l = 0), float64"""
+    lam = np.asarray(eigenvalues, np.float64)
+    l1, l2, l3 = lam[..., 0], lam[..., 1], lam[..., 2]
+    tr = l1 + l2 + l3
+    with np.errstate(invalid="ignore", divide="ignore"):
+        kappa2 = np.where(tr == 0.0, 0.0, 1.5 * (l1 * l1 + l2 * l2 + l3 * l3) / np.where(tr == 0.0, 1.0, tr * tr) - 0.5)
+    return l1 - 0.5 * (l2 + l3), l2 - l3, kappa2
 
 
 class Segments:
@@ -63,6 +88,11 @@ class Segments:
         rank = np.empty(first.size, np.uint64)
         rank[np.argsort(first, kind="stable")] = np.arange(first.size, dtype=np.uint64)
         return cls._from_labels(system, rank[inverse.ravel()], group)
+
+    @classmethod
+    def from_group(cls, system, name):
+        """ONE segment holding the group `name`: from_group(s, "Protein").gyration(0, nf).rg[:, 0] is the gmx gyrate curve"""
+        return cls._from_labels(system, np.zeros(system.n_atoms, np.uint64), name)
 
     @classmethod
     def from_molecules(cls, system):
@@ -126,6 +156,43 @@ class Segments:
         if st != OK and raise_on_error:
             self.system._raise_group(st)
         return dev, st_arr
+
+    # -- shape: gyration tensor, radius of gyration, principal axes (gr_segments_gyration_batch)
+    def gyration(self, first_slot, n_frames, kind=CENTER_PBC, weighted=True, axes=False, raise_on_error=True):
+        """-> Gyration: centre, Rg, gyration tensor (and, with `axes`, eigenvalues and principal axes) of every segment in every frame.
+        NaN rows where `centers` has them; the centre is `centers`' own, bit for bit"""
+        m = len(self)
+        mom = np.zeros((n_frames, m, 10), np.float32); st_arr = np.zeros(n_frames, np.int32)
+        ax = np.zeros((n_frames, m, 12), np.float32) if axes else None
+        st = self._lib.gr_segments_gyration_batch(self._seg, first_slot, n_frames, int(kind), int(bool(weighted)), _ptr(mom), _ptr(ax), _ptr(st_arr))
+        if st != OK and raise_on_error:
+            self.system._raise_group(st)
+        return Gyration(mom, ax, st_arr)
+
+    def gyration_device(self, first_slot, n_frames, kind=CENTER_PBC, weighted=True, axes=False, raise_on_error=True):
+        """the same, left on the device: -> (pointer to [n_frames, M, 10] float32, pointer to [n_frames, M, 12] float32 or None, status);
+        valid until the next call on this object; at most one piece of frames (set_piece_frames)"""
+        mom, ax = C.c_void_p(0), C.c_void_p(0)
+        st_arr = np.zeros(n_frames, np.int32)
+        st = self._lib.gr_segments_gyration_batch_device(self._seg, first_slot, n_frames, int(kind), int(bool(weighted)), int(bool(axes)), C.byref(mom), C.byref(ax),
+                                                         None, _ptr(st_arr))
+        if st != OK and raise_on_error:
+            self.system._raise_group(st)
+        return mom, (ax if axes else None), st_arr
+
+    def set_piece_frames(self, n):
+        """frames per piece of a gyration call (0: as many as 256 MiB of moments and axes hold); results do not depend on it"""
+        self._lib.gr_segments_set_piece_frames(self._seg, int(n))
+
+    def moments_of_inertia(self, eigenvalues, masses):
+        """principal moments of inertia I_k = W (Rg^2 - lambda_k) = W (sum of the two other eigenvalues), W = the segment's total mass
+        from `masses` [n_atoms] and its atom list: eigenvalues [..., M, 3] of a mass-weighted gyration call -> float64 [..., M, 3]"""
+        lam = np.asarray(eigenvalues, np.float64)
+        masses = np.asarray(masses, np.float64)
+        if lam.shape[-2:] != (len(self), 3):
+            raise ValueError("eigenvalues [..., M, 3]")
+        total = np.array([masses[self.atoms(s).astype(np.int64)].sum() for s in range(len(self))], np.float64)
+        return total[:, None] * (lam.sum(axis=-1, keepdims=True) - lam)
 
     def get_com(self, first_slot=0, n_frames=1, **kw): return self.centers(first_slot, n_frames, CENTER_PBC, 1, **kw)
     def get_center(self, first_slot=0, n_frames=1, **kw): return self.centers(first_slot, n_frames, CENTER_PBC, 0, **kw)

@@ -579,13 +579,39 @@ int gr_gridmap_read(gr_gridmap *map, uint64_t *count, int64_t *sum_q, float *mea
  *   gr_segments_center_batch_device  the same, left on the device: *out_dev -> [n_frames][M][3], valid until the next call on the same
  *                              object, read with gr_device_read; at most 1024 frames (GR_E_INVALID_ARG beyond); *n_segments = M
  *                              (out_dev and n_segments may each be NULL).
+ *   gr_segments_gyration_batch the shape of every segment in every frame (gmx gyrate / gmx principal per residue, lipid or chain):
+ *                              moments[f][s][0..9] = the centre (0..2: the very bits gr_segments_center_batch(kind, weighted) gives, nm),
+ *                              the radius of gyration Rg (3, nm) and the gyration tensor S (4..9: xx yy zz xy xz yz, nm^2),
+ *                              S_ab = sum w (r_a - <r_a>)(r_b - <r_b>) / sum w with w the mass (weighted) or 1, Rg = sqrt(tr S).  The
+ *                              atoms are taken as x - centre (GR_CENTER_NAIVE) or as the minimum image vector from the centre
+ *                              (_ESTIMATE, _PBC: a segment split by the cell faces is measured whole); the sums are f64 and S is taken
+ *                              about the weighted MEAN of those vectors, so it does not depend on the centre's rounding or on
+ *                              _ESTIMATE being an estimate.  A diagonal entry below zero is stored as zero.  A segment of ONE atom
+ *                              has S = 0, Rg = 0, eigenvalues 0 and the identity as axes.
+ *                              axes (may be NULL) [f][s][0..11] = the eigenvalues lambda_1 >= lambda_2 >= lambda_3 of the RETURNED f32
+ *                              tensor (0..2, nm^2) and the unit eigenvectors v_1, v_2, v_3 as rows (3..11).  Sign convention: v_1 and
+ *                              v_2 are each flipped so that their component of largest magnitude is positive (the first such
+ *                              component on ties), v_3 = v_1 x v_2 (right-handed).  Equal eigenvalues keep the solver's order.
+ *                              Box checks, strict mode, slot checks, NaN rows (all 10 / 12 values of a failed segment, every
+ *                              segment of a frame that fails its box check), status_out, return value, message and
+ *                              gr_last_error_index are those of gr_segments_center_batch for the same kind.  moments == NULL or an
+ *                              unknown kind: GR_E_INVALID_ARG.  A segment above 4096 atoms is owned by one 256-lane workgroup per
+ *                              frame: a whole large system as ONE segment works but is slow.
+ *   gr_segments_gyration_batch_device  the same, left on the device: *moments_dev -> [n_frames][M][10], *axes_dev -> [n_frames][M][12]
+ *                              (NULL unless want_axes), valid until the next call on the same object, read with gr_device_read;
+ *                              at most one piece of frames (GR_E_INVALID_ARG beyond).  The pointers may each be NULL.
+ *   gr_segments_set_piece_frames  a 1024-frame segment of a gyration call is worked in PIECES of frames so that the device block
+ *                              (88 bytes per frame and segment) stays within 256 MiB (one frame if that alone is more; at most 1024
+ *                              frames); n forces pieces of n frames, 0 restores the default.  No result depends on the piece size.
+ *                              GR_SEG_STAT_LAST_PIECES: pieces of the last gyration call; GR_SEG_STAT_LAST_LAUNCHES then counts one
+ *                              kernel per class that has segments per piece, plus one for the axes per piece when asked.
  * Every segment is owned by exactly one TEAM of lanes, chosen by its size when the object is made: <= 4 atoms 4 lanes (16 segments per
  * wave at a time), <= 16 atoms 16 lanes, <= 4096 atoms one wave, larger one 256-lane workgroup; a call is one launch per class that
  * has segments.  The team adds its lanes' f64 totals in a fixed tree and runs both stages of a GR_CENTER_PBC centre back to back;
  * no atomics touch the sums, so a segment's result depends on its atoms, its class and the frame only -- not on its neighbours, the
  * batch or the run. */
 enum { GR_SEG_STAT_TEAM4 = 1, GR_SEG_STAT_TEAM16 = 2, GR_SEG_STAT_WAVE = 3, GR_SEG_STAT_WORKGROUP = 4, GR_SEG_STAT_LAST_LAUNCHES = 5,
-       GR_SEG_STAT_LAST_LAUNCH_SETS = 6 };
+       GR_SEG_STAT_LAST_LAUNCH_SETS = 6, GR_SEG_STAT_LAST_PIECES = 7 };
 gr_segments *gr_segments_create(gr_ctx *ctx, const uint64_t *offsets, const uint64_t *atoms, uint64_t n_segments, int *status);
 gr_segments *gr_segments_from_labels(gr_ctx *ctx, const char *group, const uint64_t *labels /* [n_atoms] */, int *status);
 gr_segments *gr_segments_from_molecules(gr_ctx *ctx, int *status);
@@ -598,6 +624,12 @@ int gr_segments_center_batch(gr_segments *seg, uint32_t first_slot, uint32_t n_f
                              float *out /* [n_frames][M][3] */, int *status_out /* [n_frames] or NULL */);
 int gr_segments_center_batch_device(gr_segments *seg, uint32_t first_slot, uint32_t n_frames, int kind, int weighted,
                                     float **out_dev, uint64_t *n_segments, int *status_out);
+int gr_segments_gyration_batch(gr_segments *seg, uint32_t first_slot, uint32_t n_frames, int kind, int weighted,
+                               float *moments /* [n_frames][M][10] */, float *axes /* [n_frames][M][12] or NULL */,
+                               int *status_out /* [n_frames] or NULL */);
+int gr_segments_gyration_batch_device(gr_segments *seg, uint32_t first_slot, uint32_t n_frames, int kind, int weighted, int want_axes,
+                                      float **moments_dev, float **axes_dev, uint64_t *n_segments, int *status_out);
+int gr_segments_set_piece_frames(gr_segments *seg, uint32_t n);
 
 /* ---------------------------------------------------------------- per-frame analyses over a batch of slots
  * The calls above for `n_frames` consecutive slots in ONE set of launches and one read-back (a trajectory loop of

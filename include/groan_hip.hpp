@@ -815,6 +815,31 @@ class Segments {
     }
     std::vector<float> get_com(uint32_t first_slot, uint32_t n_frames, std::vector<int> *status = nullptr) { return centers(first_slot, n_frames, CenterKind::Pbc, true, status); }
     std::vector<float> get_center(uint32_t first_slot, uint32_t n_frames, std::vector<int> *status = nullptr) { return centers(first_slot, n_frames, CenterKind::Pbc, false, status); }
+    // the shape of every segment: moments [n_frames][M][10] = centre (3, centers' own bits), Rg, gyration tensor xx yy zz xy xz yz;
+    // with `want_axes`, axes [n_frames][M][12] = eigenvalues (descending), rows v1 v2 v3 (largest component of v1 and of v2 positive,
+    // v3 = v1 x v2).  NaN rows and `status` as for centers
+    struct Gyration { std::vector<float> moments, axes; };
+    Gyration gyration(uint32_t first_slot, uint32_t n_frames, CenterKind kind = CenterKind::Pbc, bool weighted = true, bool want_axes = false, std::vector<int> *status = nullptr) {
+        Gyration g;
+        g.moments.resize((size_t)n_frames * size() * 10);
+        if (want_axes) g.axes.resize((size_t)n_frames * size() * 12);
+        std::vector<int> st(n_frames);
+        const int r = gr_segments_gyration_batch(seg_, first_slot, n_frames, (int)kind, weighted ? 1 : 0, g.moments.data(), want_axes ? g.axes.data() : nullptr, st.data());
+        detail::batch_status(r, st, status, [this](int e) { raise(e); });
+        return g;
+    }
+    // the same, left on the device until the next call on this object (read with gr_device_read); at most one piece of frames
+    struct GyrationDevice { float *moments = nullptr, *axes = nullptr; };
+    GyrationDevice gyration_device(uint32_t first_slot, uint32_t n_frames, CenterKind kind = CenterKind::Pbc, bool weighted = true, bool want_axes = false,
+                                   std::vector<int> *status = nullptr) {
+        GyrationDevice g;
+        std::vector<int> st(n_frames);
+        const int r = gr_segments_gyration_batch_device(seg_, first_slot, n_frames, (int)kind, weighted ? 1 : 0, want_axes ? 1 : 0, &g.moments, &g.axes, nullptr, st.data());
+        detail::batch_status(r, st, status, [this](int e) { raise(e); });
+        return g;
+    }
+    // frames per piece of a gyration call; 0: as many as 256 MiB hold
+    void set_piece_frames(uint32_t n) { const int st = gr_segments_set_piece_frames(seg_, n); if (st != GR_OK) raise(st); }
     gr_segments *raw() const { return seg_; }
 
   private:

@@ -53,6 +53,7 @@ pub const GR_SEG_STAT_WAVE: c_int = 3;
 pub const GR_SEG_STAT_WORKGROUP: c_int = 4;
 pub const GR_SEG_STAT_LAST_LAUNCHES: c_int = 5;
 pub const GR_SEG_STAT_LAST_LAUNCH_SETS: c_int = 6;
+pub const GR_SEG_STAT_LAST_PIECES: c_int = 7;
 pub const GR_RG_STAT_LAST_LAUNCHES: c_int = 1;
 pub const GR_RG_STAT_LAST_PIECES: c_int = 2;
 pub const GR_RG_STAT_LAST_TOTAL: c_int = 3;
@@ -227,6 +228,12 @@ extern "C" {
     pub fn gr_segments_center_batch(seg: *mut gr_segments, first_slot: u32, n_frames: u32, kind: c_int, weighted: c_int, out: *mut c_float, status_out: *mut c_int) -> c_int;
     pub fn gr_segments_center_batch_device(seg: *mut gr_segments, first_slot: u32, n_frames: u32, kind: c_int, weighted: c_int,
                                            out_dev: *mut *mut c_float, n_segments: *mut u64, status_out: *mut c_int) -> c_int;
+    // ... and their shape: centre, Rg and gyration tensor ([n_frames][M][10]), eigenvalues and principal axes ([n_frames][M][12])
+    pub fn gr_segments_gyration_batch(seg: *mut gr_segments, first_slot: u32, n_frames: u32, kind: c_int, weighted: c_int, moments: *mut c_float, axes: *mut c_float,
+                                      status_out: *mut c_int) -> c_int;
+    pub fn gr_segments_gyration_batch_device(seg: *mut gr_segments, first_slot: u32, n_frames: u32, kind: c_int, weighted: c_int, want_axes: c_int,
+                                             moments_dev: *mut *mut c_float, axes_dev: *mut *mut c_float, n_segments: *mut u64, status_out: *mut c_int) -> c_int;
+    pub fn gr_segments_set_piece_frames(seg: *mut gr_segments, n: u32) -> c_int;
     // Region: group_iter(..).filter_geometry(..) / group_create_from_geometries for every frame of a block of resident slots
     pub fn gr_region_create(ctx: *mut gr_ctx, shapes: *const gr_shape, n_shapes: usize, naive: c_int, status: *mut c_int) -> *mut gr_region;
     pub fn gr_region_destroy(r: *mut gr_region);
