@@ -46,7 +46,10 @@ struct gr_covar {
     uint64_t ntri = 0;                    // blocks stored: nblk (nblk + 1) / 2
     grbuf::Dev<float> o, panel;           // [rpad], [rpad][GR_MAX_BATCH]
     grbuf::Dev<double> Q;                 // [ntri][GR_CV_BLOCK_LEN]
-    uint64_t n = 0;                       // counted frames
+    grbuf::Pinned<double> q_host;         // cv_get's copy of Q.  Pinned and kept: a pageable block of this size is registered with the driver for
+                                          // the copy, and freeing it right after makes the driver evict the process's queues -- the next launch of
+                                          // the context then waits some 20 ms for their restore (seen as a resident pass that misses its poll)
+    uint64_t n = 0;                      // counted frames
     uint32_t product_groups = 0, check_groups = 0;    // gr_covar_set_launch; 0: the default
     uint32_t last_product = 0, last_check = 0;        // grids of the last segment that was launched
     uint64_t launches = 0;
@@ -163,8 +166,9 @@ int cv_get(gr_covar *f, float *o, double *s, double *Q) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (o) HIPCHK(c, hipMemcpy(o, f->o.get(), (size_t)f->D * sizeof(float), hipMemcpyDeviceToHost));
     if (!s && !Q) return GR_OK;
-    std::vector<double> q(cv_q_len(f));
-    HIPCHK(c, hipMemcpy(q.data(), f->Q.get(), q.size() * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(c, f->q_host.reserve(cv_q_len(f), grbuf::exact));
+    const double *q = f->q_host.get();
+    HIPCHK(c, hipMemcpy(f->q_host.get(), f->Q.get(), cv_q_len(f) * sizeof(double), hipMemcpyDeviceToHost));
     const uint32_t D = f->D;
     if (s) for (uint32_t i = 0; i < D; ++i) s[i] = q[cv_at(f, i, D)];
     if (Q)

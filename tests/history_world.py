@@ -11,12 +11,24 @@ to write are repeated there with copy_frame, as test_gpu_xtc_encoder_device.py r
 A kind is a function (world) -> result.  It first puts back, from the pristine host frames, every slot it reads or writes that an
 earlier kind has changed (`World.need`; by set_frame or by upload_async + upload_wait, fixed per kind), makes its calls and returns
 everything they handed back: arrays, statuses, the exception if one was raised (with its atom index), and positions and box of every slot
-it may write.  A kind leaves groups, bonds, masses and tuning as it found them."""
+it may write.  A kind leaves groups, bonds, masses and tuning as it found them.
+
+The family "series" holds the objects that keep state over the frames handed to them -- Fluctuations (groups of all three snapshot
+forms), Covariance, MSD, VectorCorrelation, Internals, RMSDPanel -- and the topology family `Segments.gyration` on the segments of
+`centers` plus `sizes` (1 to 4 097 consecutive atoms: every team class of the moments kernel).  The world makes each of them on
+first use (`World.fluct`, `.covar`, `.msd`, `.vcorr`, `.internals`, `.panel`, `.segments`), so a fresh world of another kind pays nothing
+for them and the order of creation differs between a fresh world and the long-lived one.  Every kind on such an object starts with
+clear() and returns statuses, the raw state and the closed results; MSD and VectorCorrelation kinds stay inside one cell (the
+whole configuration moves between slot 7 and slot 8).  A call that is refused outright (capacity, changed masses) puts its status
+in front of the frames' statuses in `st` and its exception in `refused`.  rmsd_matrix(rows, cols) needs panels of equally many
+atoms, so the columns panel on `small` (capacity 8) meets a rows panel on `small`; `big` against it is the refused call.
+ADJACENCIES 11-19 stand behind the shortcuts of these objects; each says which."""
 import functools
 import os
 
 import numpy as np
 
+from groan_rs_amd import _lib as LIB
 from groan_rs_amd._lib import E_GROUP_NOT_FOUND, E_HIP, E_NO_BOX, E_NO_POSITION, E_OUT_OF_RANGE, E_UNSUPPORTED_BOX     # the status codes of include/groan_hip.h, for the tests too
 
 F = np.float32
@@ -39,6 +51,11 @@ N_XTC = 6
 CT_CUTOFF, CT_BINS = 0.3, 40
 REGION_SPECS = [dict(kind="sphere", position=[2.6, 2.8, 2.2], radius=1.6),                       # a sphere and a cylinder along z, both inside the filled part of the cell
                 dict(kind="cylinder", position=[2.4, 2.6, 0.8], radius=1.2, height=3.0, orientation="z")]
+SERIES_CAPACITY, PANEL_SMALL_CAPACITY = 16, 8
+SERIES_MOLS = tuple(range(0, N_MOL, 10))                                                         # the molecules whose O-H1 vectors and internal coordinates are followed
+SIZES = (1, 5, 17, 65, 257, 4097)                                                                # the segments of seg["sizes"], cut from consecutive atoms: every team class of k_segment_moments
+NAN_SERIES = 3 * 200 + 1                                                                         # H1 of a followed molecule
+DIHEDRAL_MIN_SINE = 0.3
 NAIVE, ESTIMATE, PBC = 0, 1, 2
 CENTRES = [(NAIVE, 0), (NAIVE, 1), (ESTIMATE, 0), (ESTIMATE, 1), (PBC, 0), (PBC, 1)]
 
@@ -104,6 +121,37 @@ def host_world():
                 xtc_frames=xtc_frames, donors=donors)
 
 
+def bend_sines(tuples, frames=range(N_FRAMES)):
+    """[len(frames), T, 2]: the sines of the two bend angles i-j-k and j-k-l of the dihedral tuples, minimum image, in f64"""
+    h = host_world()
+    t = np.asarray(tuples, np.int64)
+    out = []
+    for f in frames:
+        x, H = h["frames"][f].astype(np.float64), cell(h["boxes"][f])
+        def d(a, b):
+            v = x[b] - x[a]
+            return v - np.round(v @ np.linalg.inv(H)) @ H
+        def sine(u, v):
+            return np.linalg.norm(np.cross(u, v), axis=1) / (np.linalg.norm(u, axis=1) * np.linalg.norm(v, axis=1))
+        out.append(np.stack([sine(d(t[:, 1], t[:, 0]), d(t[:, 1], t[:, 2])), sine(d(t[:, 2], t[:, 1]), d(t[:, 2], t[:, 3]))], 1))
+    return np.stack(out)
+
+
+@functools.lru_cache(maxsize=None)
+def series_tuples():
+    """-> dict: pairs [401, 2] O-H1 and angles [401, 3] H1-O-H2 of every 10th molecule; dihedrals [<= 400, 4] H2-O...O'-H2' of the placed
+    donor-acceptor pairs (not H1: it lies on the line O...O'), without those whose bend angles come near 0 or 180 degrees in some
+    frame; sizes: the atom lists of the segments of SIZES"""
+    h = host_world()
+    o = 3 * np.array(SERIES_MOLS, np.int64)
+    d = 3 * h["donors"].astype(np.int64)
+    dih = np.stack([d + 2, d, d + 3, d + 5], 1)
+    dih = dih[(bend_sines(dih) >= DIHEDRAL_MIN_SINE).all(axis=(0, 2))]
+    off = np.concatenate([[0], np.cumsum(SIZES)])
+    return dict(pairs=np.stack([o, o + 1], 1).astype(np.uint64), angles=np.stack([o + 1, o, o + 2], 1).astype(np.uint64), dihedrals=dih.astype(np.uint64),
+                sizes=[np.arange(off[k], off[k + 1], dtype=np.uint64) for k in range(len(SIZES))])
+
+
 def nan_frame(slot, atom):
     x = host_world()["frames"][slot].copy()
     x[atom] = np.nan
@@ -150,9 +198,44 @@ class World:
                     wt.write_frame(x[::-1].copy(), box9, step=10 * f, time=0.5 * f)
         self.xtc, self.trr = G.XtcFile(self.xtc_path), G.TrrFile(self.trr_path)
         self.n_written = 0
+        self.made = {}            # the series objects, made on first use: a fresh world of another kind pays nothing for them
         self.s.sync()
 
+    def _once(self, key, make):
+        if key not in self.made:
+            self.made[key] = make()
+        return self.made[key]
+
+    def fluct(self, group):
+        return self._once(("fluct", group), lambda: self.G.Fluctuations(self.s, group))
+
+    def covar(self, group):
+        return self._once(("covar", group), lambda: self.G.Covariance(self.s, group))
+
+    def msd(self, group):
+        """`small` with nojump, `masked` lateral and as the positions stand"""
+        kw = dict(dims="xyz", nojump=True) if group == "small" else dict(dims="xy", nojump=False)
+        return self._once(("msd", group), lambda: self.G.MSD(self.s, group, SERIES_CAPACITY, **kw))
+
+    def vcorr(self):
+        return self._once(("vcorr",), lambda: self.G.VectorCorrelation(self.s, series_tuples()["pairs"], SERIES_CAPACITY, rank=(1, 2), pbc=True))
+
+    def internals(self, which):
+        tuples = series_tuples()[{"distance": "pairs", "angle": "angles", "dihedral": "dihedrals"}[which]]
+        return self._once(("internals", which), lambda: self.G.Internals(self.s, which, tuples))
+
+    def panel(self, which):
+        group, capacity = {"big": ("big", SERIES_CAPACITY), "small": ("small", PANEL_SMALL_CAPACITY), "small16": ("small", SERIES_CAPACITY)}[which]
+        return self._once(("panel", which), lambda: self.G.RMSDPanel(self.s, group, capacity))
+
+    def segments(self, which):
+        if which == "sizes" and which not in self.seg:
+            self.seg[which] = self.G.Segments.from_lists(self.s, series_tuples()["sizes"])
+        return self.seg[which]
+
     def close(self):
+        for obj in self.made.values():
+            obj.close()
         self.xtc.close(); self.trr.close()
         self.s.close(); self.ref.close()
         self.G.pinned_free(self._pin_ptr)
@@ -643,6 +726,298 @@ def _(w, out):
         out[name] = a
 
 
+def _gyration(which, first, nf, axes, piece=0):
+    def body(w, out):
+        seg = w.segments(which)
+        if piece:                                          # (sticky: put back below; a kind without a piece size takes the object as it finds it)
+            seg.set_piece_frames(piece)
+        try:
+            g = seg.gyration(first, nf, axes=axes)
+        finally:
+            if piece:
+                seg.set_piece_frames(0)
+        out["moments"], out["st"] = g.moments, g.status
+        if axes:
+            out["raw_axes"] = g.raw_axes
+    return body
+
+
+kind("gyr_mol_9_axes", "topology", slots=tuple(range(4, 13)))(_gyration("mol", 4, 9, True))
+kind("gyr_resid_2", "topology", slots=(7, 8), how="upload")(_gyration("resid", 7, 2, False))
+kind("gyr_sizes_16_axes", "topology", slots=R16, how="upload")(_gyration("sizes", 0, 16, True))
+kind("gyr_mol_9_pieces", "topology", slots=tuple(range(4, 13)))(_gyration("mol", 4, 9, True, piece=2))
+
+
+@kind("gyr_sizes_device_4", "topology", slots=(6, 7, 8, 9), how="upload")
+def _(w, out):
+    seg = w.segments("sizes")
+    mom, ax, out["st"] = seg.gyration_device(6, 4, axes=True)
+    out["moments"], out["raw_axes"] = w.s.device_read(mom, 0, (4, len(seg), 10)), w.s.device_read(ax, 0, (4, len(seg), 12))
+
+
+@kind("fail_gyr_mixed", "topology", writes=(5, 6), failing=True)
+def _(w, out):
+    w.need((4, 7, 8), "set_frame")
+    w.load(5, "set_frame", box=None)                                                # the pieces are slots 4-5, 6-7 and 8: one failure on either side of the first boundary
+    w.load(6, "set_frame", frame=nan_frame(6, NAN_BIG))
+    seg = w.segments("mol")
+    seg.set_piece_frames(2)
+    try:
+        g = seg.gyration(4, 5, axes=True, raise_on_error=False)
+    finally:
+        seg.set_piece_frames(0)
+    out["moments"], out["raw_axes"], out["st"] = g.moments, g.raw_axes, g.status
+
+
+# -- series: the objects that keep state over the frames handed to them.  Every kind starts with clear()
+def _fluct_state(f, out, tag=""):
+    out["origin" + tag], out["sum" + tag], out["sq" + tag], out["n" + tag] = f.raw()
+    out["mean" + tag], out["rmsf" + tag], out["n_frames" + tag] = f.mean(), f.rmsf(), f.n_frames
+
+
+def _fluct(group, calls):
+    def body(w, out):
+        f = w.fluct(group)
+        f.clear()
+        out["cleared_origin"], out["cleared_n"] = f.raw()[0], f.n_frames
+        out["st"] = np.concatenate([f.accumulate(first, nf) for first, nf in calls])
+        _fluct_state(f, out)
+    return body
+
+
+kind("fluct_small_8", "series", slots=ORTHO8)(_fluct("small", [(0, 8)]))
+kind("fluct_masked_16", "series", slots=R16, how="upload")(_fluct("masked", [(0, 16)]))
+kind("fluct_list_tric_8", "series", slots=TRIC8, how="upload")(_fluct("list", [(8, 8)]))
+kind("fluct_two_calls", "series", slots=R16)(_fluct("list", [(0, 5), (5, 11)]))
+
+
+@kind("fail_fluct_nan", "series", writes=(4,), failing=True)
+def _(w, out):
+    w.need((1, 2, 3, 5, 6, 7, 8), "set_frame")
+    w.load(4, "set_frame", frame=nan_frame(4, NAN_SMALL))
+    f = w.fluct("small")
+    f.clear()
+    f.accumulate(1, 3); f.accumulate(5, 4)                                          # the call below without its failed frame
+    _fluct_state(f, out, "_without")
+    f.clear()
+    out["st"] = f.accumulate(1, 8, raise_on_error=False)                            # the object's last call: 8 frames, one of them failed
+    _fluct_state(f, out)
+
+
+def _covar_state(cv, out):
+    out["origin"], out["sum"], out["q"], out["n"] = cv.raw()
+    out["cov"], out["cov_mw"], out["dccm"], out["mean"] = cv.matrix(), cv.matrix(mass_weighted=True), cv.dccm(), cv.mean()
+
+
+def _covar(group, first, nf):
+    def body(w, out):
+        cv = w.covar(group)
+        cv.clear()
+        out["st"] = cv.accumulate(first, nf)
+        _covar_state(cv, out)
+    return body
+
+
+kind("covar_small_16", "series", slots=R16)(_covar("small", 0, 16))
+kind("covar_a300_tric_8", "series", slots=TRIC8, how="upload")(_covar("a300", 8, 8))
+
+
+@kind("fail_covar_all_bad", "series", writes=(2, 3), failing=True)
+def _(w, out):
+    w.need((4, 5, 6, 7), "set_frame")
+    w.load(2, "set_frame", frame=nan_frame(2, 310))
+    w.load(3, "set_frame", frame=nan_frame(3, 599))
+    cv = w.covar("a300")
+    cv.clear()
+    out["st"] = cv.accumulate(2, 2, raise_on_error=False)
+    out["n_bad"] = cv.n_frames
+    out["st_good"] = cv.accumulate(4, 4)                                            # the origin is this call's first frame
+    _covar_state(cv, out)
+
+
+def _msd_state(m, out, tag=""):
+    out["disp" + tag], out["from_origin" + tag] = m.displacements(0, m.n_frames), m.from_origin()
+    out["msd" + tag], out["pairs" + tag] = m.msd()
+    out["msd3" + tag], out["pairs3" + tag] = m.msd(3)
+    out["n_pad"] = m.stat(LIB.MSD_STAT_N_PAD)
+
+
+def _msd(group, calls):
+    def body(w, out):
+        m = w.msd(group)
+        m.clear()
+        out["st"] = np.concatenate([m.append(first, nf) for first, nf in calls])
+        _msd_state(m, out)
+    return body
+
+
+kind("msd_small_ortho_8", "series", slots=ORTHO8)(_msd("small", [(0, 8)]))
+kind("msd_masked_tric_8", "series", slots=TRIC8, how="upload")(_msd("masked", [(8, 8)]))
+kind("msd_appended_in_three", "series", slots=ORTHO8)(_msd("small", [(0, 3), (3, 1), (4, 4)]))
+
+
+@kind("fail_msd_nobox", "series", writes=(2,), failing=True)
+def _(w, out):
+    w.need((0, 1, 3), "set_frame")
+    w.load(2, "set_frame", box=None)
+    m = w.msd("small")
+    m.clear()
+    out["st"] = m.append(0, 4, raise_on_error=False)                                # nojump needs the frame's box
+    _msd_state(m, out)
+
+
+@kind("fail_msd_capacity", "series", slots=ORTHO8, failing=True)
+def _(w, out):
+    m = w.msd("small")
+    m.clear()
+    st = [m.append(0, 8), m.append(0, 8)]                                           # full
+    _msd_state(m, out, "_before")
+    try:
+        m.append(0, 1)
+        refused = 0
+    except w.G.GroanError as e:
+        out["refused"], refused = _exc(e), e.status
+    out["st"] = np.concatenate(st + [[refused]]).astype(np.int32)                   # the frames' statuses, then the refused call's
+    out["n_frames"] = m.n_frames
+    _msd_state(m, out)
+
+
+def _vcorr_state(v, out):
+    out["vectors"] = v.vectors(0, v.n_frames)
+    out["c1"], out["c2"], out["pairs"] = v.correlate()
+    out["each1"], out["each2"] = v.correlate_each(4)
+    out["n_pad"] = v.stat(LIB.VCORR_STAT_N_PAD)
+
+
+def _vcorr(first, nf):
+    def body(w, out):
+        v = w.vcorr()
+        v.clear()
+        out["st"] = v.append(first, nf)
+        _vcorr_state(v, out)
+    return body
+
+
+kind("vcorr_ortho_8", "series", slots=ORTHO8, how="upload")(_vcorr(0, 8))
+kind("vcorr_tric_8", "series", slots=TRIC8)(_vcorr(8, 8))
+
+
+@kind("fail_vcorr_nan", "series", writes=(2,), failing=True)
+def _(w, out):
+    w.need((0, 1, 3), "set_frame")
+    w.load(2, "upload", frame=nan_frame(2, NAN_SERIES))
+    v = w.vcorr()
+    v.clear()
+    out["st"] = v.append(0, 4, raise_on_error=False)
+    _vcorr_state(v, out)
+
+
+def _internals(which, first, nf):
+    def body(w, out):
+        out["v"], out["st"] = w.internals(which).values(first, nf)
+    return body
+
+
+kind("internals_distance_16", "series", slots=R16)(_internals("distance", 0, 16))
+kind("internals_angle_16", "series", slots=R16, how="upload")(_internals("angle", 0, 16))
+kind("internals_dihedral_8", "series", slots=ORTHO8, how="upload")(_internals("dihedral", 0, 8))
+
+
+def _internals_state(ic, out, tag):
+    out["mean_" + tag], out["var_" + tag] = ic.read()
+    out["origin_" + tag], out["sum_" + tag], out["sq_" + tag], out["n_" + tag] = ic.read_raw()
+
+
+@kind("internals_accumulate_16", "series", slots=R16)
+def _(w, out):
+    st = []
+    for which in ("angle", "dihedral"):
+        ic = w.internals(which)
+        ic.clear()
+        st.append(ic.accumulate(0, 16))
+        _internals_state(ic, out, which)
+    out["st"] = np.concatenate(st)
+    out["v_dihedral"] = w.internals("dihedral").values(0, 16)[0]                    # the rows the sums are made of (slots 8-15: no other kind returns them)
+
+
+@kind("fail_internals_nan", "series", writes=(5,), failing=True)
+def _(w, out):
+    w.need((4, 6), "set_frame")
+    w.load(5, "set_frame", frame=nan_frame(5, int(series_tuples()["dihedrals"][3, 3])))
+    ic = w.internals("dihedral")
+    out["v"], out["st_values"] = ic.values(4, 3, raise_on_error=False)
+    ic.clear()
+    out["st"] = ic.accumulate(4, 3, raise_on_error=False)
+    _internals_state(ic, out, "dihedral")
+
+
+def _panel_state(w, p, out):
+    out["status"], out["m"] = p.status, w.G.rmsd_matrix(p)
+
+
+@kind("panel_big_16", "series", slots=R16)
+def _(w, out):
+    p = w.panel("big")
+    p.clear()
+    out["st"] = p.append(0, 16)
+    _panel_state(w, p, out)
+
+
+@kind("panel_big_small_cols", "series", slots=R16, how="upload")
+def _(w, out):
+    big, rows, cols = w.panel("big"), w.panel("small16"), w.panel("small")
+    for p in (big, rows, cols):
+        p.clear()
+    out["st"] = np.concatenate([big.append(8, 8), rows.append(0, 16), cols.append(4, 8)])
+    out["m_big"] = w.G.rmsd_matrix(big)
+    out["m"] = w.G.rmsd_matrix(rows, cols)
+    out["m_t"] = w.G.rmsd_matrix(cols, rows)
+    try:                                                                            # panels of different groups are refused, and nothing changes
+        w.G.rmsd_matrix(big, cols)
+    except w.G.GroanError as e:
+        out["refused"] = _exc(e)
+    out["m_again"] = w.G.rmsd_matrix(rows, cols)
+
+
+@kind("panel_device", "series", slots=TRIC8)
+def _(w, out):
+    p = w.panel("big")
+    p.clear()
+    out["st"] = p.append(8, 8)
+    dev, nr, nc = w.G.rmsd_matrix(p, device=True)
+    out["shape"], out["m"] = (nr, nc), w.s.device_read(dev, 0, (nr, nc))
+    out["status"] = p.status
+
+
+@kind("fail_panel_nan", "series", writes=(3,), failing=True)
+def _(w, out):
+    w.need((2, 4), "set_frame")
+    w.load(3, "set_frame", frame=nan_frame(3, NAN_BIG))
+    p = w.panel("big")
+    p.clear()
+    out["st"] = p.append(2, 3, raise_on_error=False)                                # the failed frame takes a row all the same
+    out["len"] = len(p)
+    _panel_state(w, p, out)
+
+
+@kind("fail_panel_masses", "series", slots=(0, 1, 2, 3), failing=True)
+def _(w, out):
+    p = w.panel("big")
+    p.clear()
+    other = (w.host["masses"][::-1] * F(1.5)).astype(F)
+    refused = 0
+    try:
+        w.s.set_masses(other)
+        p.append(0, 2)
+    except w.G.GroanError as e:
+        out["refused"], refused = _exc(e), e.status
+    finally:
+        w.s.set_masses(w.host["masses"])
+    out["len_refused"] = len(p)
+    out["st"] = np.concatenate([[refused], p.append(0, 4)]).astype(np.int32)        # the refused call's status, then the frames of the good one
+    _panel_state(w, p, out)
+
+
 # -- trajectory I/O
 def _xtc_write(count, repeat):
     def body(w, out):
@@ -791,6 +1166,26 @@ ADJACENCIES = {
     8: ["whole_mols", "rebond_whole", "whole_mols"],
     9: ["res_fit_3", "plan_rmsd_masked", "res_fit_9", "plan_rmsd_masked", "res_fit_2"],
     10: ["fail_contacts_nan", "contacts_pairs_8", "region_select_16", "contacts_pairs_8"],
+    # 11: the verdict block of an object and its "skip" tail, reused by every call (GrVerdicts): a call of as many frames as the failed
+    #     one before it on the same object; clear() behind a failed call gives the origin back
+    11: ["fail_fluct_nan", "fluct_masked_16", "fluct_small_8", "fluct_masked_16"],
+    # 12: RMSDPanel.append packs through the context's shared state words (states_from_prechecks, pbc_center_stages, fetch_states):
+    #     the resident kinds behind it must still start lean, the plans still read their own states
+    12: ["res_fit_9", "panel_big_16", "res_fit_3", "plan_rmsd_big", "panel_big_16", "atoms_center_batch_res"],
+    # 13: the panel looks at its weights again only when the context's epoch has moved; Covariance keeps the masses it was made with
+    13: ["masses_changed", "panel_big_16", "fail_panel_masses", "panel_big_16", "covar_small_16"],
+    # 14: every series object keeps a snapshot (GrSnapshot) of its group, which is replaced and put back around it
+    14: ["fail_redefined_small_plan", "fluct_small_8", "msd_small_ortho_8", "restored_small_plan", "covar_small_16"],
+    # 15: gyration and centers share key_dev, ok_dev, ok_host and the launch statistics of one Segments object; piece_frames is sticky
+    15: ["seg_mol_9", "gyr_mol_9_pieces", "seg_mol_1", "gyr_mol_9_axes", "fail_seg_nobox", "gyr_mol_9_axes", "fail_gyr_mixed", "seg_mol_9"],
+    # 16: the grow-only gyr block grows and is then reused by a smaller call
+    16: ["gyr_sizes_16_axes", "gyr_sizes_device_4", "gyr_resid_2", "gyr_sizes_16_axes"],
+    # 17: the band scratch of the Gram kernel and the panels of the two band objects (MSD, VectorCorrelation)
+    17: ["msd_masked_tric_8", "vcorr_tric_8", "msd_appended_in_three", "vcorr_ortho_8"],
+    # 18: slots rewritten by another call and put back; the accumulator of Internals behind a failed call
+    18: ["whole_mols", "internals_dihedral_8", "fail_internals_nan", "internals_accumulate_16", "internals_dihedral_8"],
+    # 19: device ingest into the slots straight in front of an object's walk (SlotUse)
+    19: ["xtc_read_full", "fluct_small_8", "trr_read", "panel_big_16"],
 }
 
 

@@ -1,12 +1,19 @@
 """A call's result does not depend on what its context did before.
 
 tests/history_world.py builds one world and a table of call kinds over every family of the library (centres, RMSD, pair distances,
-topology, trajectory I/O, failing calls, redefinitions).  Every kind runs on two fresh worlds of its own: those two results must
+topology with gyration, trajectory I/O, failing calls, redefinitions, and "series": RMSDPanel, Fluctuations, Covariance, MSD, Internals,
+VectorCorrelation on long-lived objects).  Every kind runs on two fresh worlds of its own: those two results must
 agree, bit for bit wherever the project documents determinism (everything but the RMSD calls); an RMSD kind whose fresh results differ
 is held to the margins of tests/test_gpu_resident.py (RMSD 2e-6 nm, fitted coordinates 2e-5 nm; rotation elements 2e-6 as in
 tests/test_gpu_rmsd_fast.py) from then on.  The fresh result is checked once against the reference the suite uses for that call.
 Then ONE long-lived world walks the mandatory adjacencies (each behind a shortcut of the library: an elided reset, a shared
-sequence word, a grow-only buffer, a cache) and two seeded schedules, and every step must give its kind's fresh result."""
+sequence word, a grow-only buffer, a cache; 11-19 behind those of the series objects and gyration: the verdict block and its tail,
+the context's state words behind a panel append, the epoch check, group snapshots, the words gyration shares with centers, the
+grow-only gyration block, the band scratch, rewritten slots, device ingest) and two seeded schedules, and every step must give its
+kind's fresh result.  The series kinds are compared as their objects' own suites compare (cited where used): bit for bit for the
+Fluctuations and Internals sums, MSD displacements and VectorCorrelation vectors inside the cell, within the reference modules'
+derived bounds elsewhere.  (test_gpu_internals.py holds `values` to internals_ref.bounds of the f64 values, not to values32's bits:
+so does this file.)"""
 import itertools
 import os
 import time
@@ -15,10 +22,17 @@ import traceback
 import numpy as np
 import pytest
 
+import covar_ref
+import fluct_ref
 import gridmap_ref
+import gyration_ref
 import hbond_ref
 import history_world as HW
+import internals_ref
+import msd_ref
 import oracle_lib as O
+import rmsd_matrix_ref
+import vcorr_ref
 import whole_ref
 
 pytestmark = pytest.mark.gpu
@@ -421,6 +435,248 @@ def _check_topology(G, fresh, h):
     assert np.array_equal(r["counts"], ref.count) and np.array_equal(r["sums_q"], ref.sum_q) and np.array_equal(r["mean"].view(np.uint32), ref.mean().view(np.uint32))
 
 
+def _check_gyration(fresh, h):
+    t = HW.series_tuples()
+    lists = {"mol": [np.arange(3 * k, 3 * k + 3) for k in range(HW.N_MOL)], "resid": [np.arange(7 * k, min(7 * k + 7, HW.N)) for k in range((HW.N + 6) // 7)],
+             "sizes": [l.astype(np.int64) for l in t["sizes"]]}
+    flat = {which: gyration_ref.flatten(l) for which, l in lists.items()}
+
+    def frame(what, which, r, k, f, pos=None, box=None, axes=True):
+        """frame k of the result r = slot f: the moments against the reference (gyration_ref's derived margin), the axes against the
+        returned tensor, and their directions where the reference's eigenvalues stand apart (test_gpu_gyration.py; for `sizes` that
+        is one axis per segment, test_history_schedule.py says which)"""
+        pos, box = h["frames"][f] if pos is None else pos, h["boxes"][f] if box is None else box
+        S_ref, margin = gyration_ref.reference(pos, box, h["masses"], flat[which], r["moments"][k, :, 0:3], HW.PBC, True)
+        gyration_ref.check_moments(what, r["moments"][k], S_ref, margin)
+        if axes:
+            gyration_ref.check_axes(what, r["moments"][k], r["raw_axes"][k], S_ref)
+
+    r = fresh.result["gyr_mol_9_axes"]
+    assert r["raised"] is None and (r["st"] == 0).all() and r["moments"].shape == (9, HW.N_MOL, 10) and r["raw_axes"].shape == (9, HW.N_MOL, 12)
+    assert np.array_equal(r["moments"][..., 0:3].view(np.uint32), fresh.result["seg_mol_9"]["c"].view(np.uint32))     # the centre is `centers`' own, bit for bit
+    for k in range(9):                                                          # (the directions in three frames, both cells among them)
+        frame("mol slot %d" % (4 + k), "mol", r, k, 4 + k, axes=k in (0, 4, 8))
+    p = fresh.result["gyr_mol_9_pieces"]                                        # results do not depend on the piece size
+    assert p["raised"] is None and all(np.array_equal(p[label].view(np.uint32), r[label].view(np.uint32)) for label in ("moments", "raw_axes", "st"))
+    r = fresh.result["gyr_resid_2"]
+    assert r["raised"] is None and (r["st"] == 0).all() and "raw_axes" not in r
+    assert np.array_equal(r["moments"][..., 0:3].view(np.uint32), fresh.result["seg_resid_2"]["c"].view(np.uint32))
+    for k in range(2):
+        frame("resid slot %d" % (7 + k), "resid", r, k, 7 + k, axes=False)
+    r = fresh.result["gyr_sizes_16_axes"]
+    assert r["raised"] is None and (r["st"] == 0).all() and r["moments"].shape == (16, len(HW.SIZES), 10)
+    assert (r["moments"][:, 0, 3:] == 0).all() and np.array_equal(r["raw_axes"][:, 0, 3:], np.broadcast_to(np.eye(3, dtype=F).ravel(), (16, 9)))    # one atom
+    for k in range(16):
+        frame("sizes slot %d" % k, "sizes", r, k, k)
+        want = np.stack([O.get_center(h["frames"][k], l.astype(np.uint64), h["boxes"][k], h["masses"]) for l in lists["sizes"]])     # no `centers` kind runs on these segments
+        assert _lattice_error(r["moments"][k, :, 0:3], want, h["boxes"][k]) <= REF_CENTRE, k
+    d = fresh.result["gyr_sizes_device_4"]                                      # the device form: the host form's bits
+    assert d["raised"] is None and (d["st"] == 0).all()
+    assert np.array_equal(d["moments"].view(np.uint32), r["moments"][6:10].view(np.uint32)) and np.array_equal(d["raw_axes"].view(np.uint32), r["raw_axes"][6:10].view(np.uint32))
+    # the mixed batch: a frame without box is NaN throughout, a missing position costs its own molecule only; the good frames are the good call's
+    r, good = fresh.result["fail_gyr_mixed"], fresh.result["gyr_mol_9_axes"]
+    assert r["raised"] is None and r["st"].tolist() == [0, E_NO_BOX, E_NO_POSITION, 0, 0]
+    assert np.isnan(r["moments"][1]).all() and np.isnan(r["raw_axes"][1]).all()
+    hit = np.zeros(HW.N_MOL, bool); hit[HW.NAN_BIG // 3] = True
+    assert np.isnan(r["moments"][2][hit]).all() and np.isnan(r["raw_axes"][2][hit]).all() and not np.isnan(r["moments"][2][~hit]).any()
+    for label in ("moments", "raw_axes"):
+        assert np.array_equal(r[label][[0, 3, 4]].view(np.uint32), good[label][[0, 3, 4]].view(np.uint32)), label
+        assert np.array_equal(r[label][2][~hit].view(np.uint32), good[label][2][~hit].view(np.uint32)), label
+
+
+def _box9(box):
+    b = np.zeros(9, F); b[:len(box)] = box
+    return b
+
+
+def _check_series(G, fresh, h):
+    t = HW.series_tuples()
+    frames, boxes = h["frames"], [_box9(b) for b in h["boxes"]]
+    bits = fluct_ref.same_bits
+
+    # -- Fluctuations: the raw state is the restatement's walk bit for bit, the closing within 1e-12 of its closing (test_gpu_fluct.py)
+    def fluct_state(r, tag, group, fr):
+        idx = h["groups"][group]
+        ref = fluct_ref.State(len(idx))
+        st, bad = ref.accumulate(fr, idx)
+        assert r["n" + tag] == ref.n == r["n_frames" + tag], (group, tag)
+        assert bits(r["origin" + tag], ref.o) and bits(r["sum" + tag], ref.s) and bits(r["sq" + tag], ref.q), (group, tag)
+        mean, var, rmsf = ref.close()
+        assert np.abs(r["mean" + tag] - mean).max() <= 1e-12 and np.abs(r["rmsf" + tag] - rmsf).max() <= 1e-12, (group, tag)
+        return st
+    for name, group, slots in (("fluct_small_8", "small", range(8)), ("fluct_masked_16", "masked", range(16)), ("fluct_list_tric_8", "list", range(8, 16)),
+                               ("fluct_two_calls", "list", range(16))):
+        r = fresh.result[name]
+        assert r["raised"] is None and r["cleared_n"] == 0 and not r["cleared_origin"].any(), name
+        assert np.array_equal(r["st"], fluct_state(r, "", group, [frames[f] for f in slots])), name
+    r = fresh.result["fail_fluct_nan"]
+    bad = [HW.nan_frame(4, HW.NAN_SMALL) if f == 4 else frames[f] for f in range(1, 9)]
+    st = fluct_state(r, "", "small", bad)
+    assert r["raised"] is None and np.array_equal(r["st"], st) and st.tolist() == [0, 0, 0, E_NO_POSITION, 0, 0, 0, 0] and r["n"] == 7
+    fluct_state(r, "_without", "small", [frames[f] for f in (1, 2, 3, 5, 6, 7, 8)])
+    for label in ("origin", "sum", "sq", "mean", "rmsf"):                        # the failed frame is counted for no atom
+        assert bits(r[label], r[label + "_without"]), label
+
+    # -- Covariance: origin and count exactly, sums within the bound of any summation order, the closings as test_gpu_covar.py holds them
+    def ulps(a, b):
+        with np.errstate(invalid="ignore"):
+            return np.abs(a - b) / np.spacing(np.maximum(np.abs(a), np.abs(b)))
+    def covar_state(r, group, fr):
+        idx = h["groups"][group]
+        ref = covar_ref.State(len(idx))
+        st, bad = ref.accumulate(fr, idx)
+        assert r["n"] == ref.n and bits(r["origin"].reshape(-1), ref.o), group
+        assert (np.abs(r["q"] - ref.Q) <= ref.q_bound()).all() and (np.abs(r["sum"].reshape(-1) - ref.s) <= ref.s_bound()).all() and np.array_equal(r["q"], r["q"].T), group
+        mean, cov = covar_ref.close(r["origin"], r["sum"], r["q"], r["n"])             # the library's closing step, applied to the device's own raw state
+        assert ulps(r["mean"], mean).max() <= 2 and ulps(r["cov"], cov).max() <= 2, group
+        rm = np.sqrt(np.repeat(h["masses"][idx].astype(np.float64), 3))
+        assert ulps(r["cov_mw"], r["cov"] * np.outer(rm, rm)).max() <= 2, group
+        want = covar_ref.dccm(covar_ref.close(ref.o, ref.s, ref.Q, ref.n)[1])
+        assert np.abs(r["dccm"] - want).max() <= 1e-12 and np.array_equal(r["dccm"], r["dccm"].T), group
+        return st
+    for name, group, slots in (("covar_small_16", "small", range(16)), ("covar_a300_tric_8", "a300", range(8, 16))):
+        r = fresh.result[name]
+        assert r["raised"] is None and np.array_equal(r["st"], covar_state(r, group, [frames[f] for f in slots])), name
+    r = fresh.result["fail_covar_all_bad"]
+    assert r["raised"] is None and r["st"].tolist() == [E_NO_POSITION, E_NO_POSITION] and r["n_bad"] == 0 and not r["st_good"].any() and r["n"] == 4
+    covar_state(r, "a300", [frames[f] for f in range(4, 8)])
+    assert bits(r["origin"], frames[4][h["groups"]["a300"]])                     # the origin comes from the good call
+
+    # -- MSD: the displacements are the restatement's walk bit for bit, the curves within msd_ref.msd_bound of the direct evaluation (test_gpu_msd.py)
+    def msd_state(r, tag, group, dims, nojump, fr, bx, n_frames):
+        idx = h["groups"][group]
+        ref = msd_ref.Walk(len(idx), dims, nojump)
+        st, bad = ref.append(fr, bx, idx)
+        panel, S, n_pad = ref.panel(), len(idx), r["n_pad"]
+        assert n_pad % 64 == 0 and 0 <= n_pad - S < 64 and len(panel) == n_frames
+        assert bits(r["disp" + tag], panel), (group, tag)
+        for label, lag in (("", None), ("3", 3)):
+            msd, pairs = r["msd" + label + tag], r["pairs" + label + tag]
+            want, wpairs, qsum = msd_ref.direct_msd(panel, ref.ok, lag, dtype=np.longdouble)
+            assert np.array_equal(pairs, wpairs) and np.array_equal(np.isnan(msd), pairs == 0) and (not pairs[0] or (msd[0] == 0.0 and not np.signbit(msd[0])))
+            have = pairs > 0
+            assert (np.abs(msd[have] - want[have]) <= msd_ref.msd_bound(qsum, pairs, n_pad, S)[have]).all(), (group, tag, label)
+        X = panel.reshape(len(panel), -1).astype(np.longdouble)
+        q, ok = np.asarray((X * X).sum(1), np.float64), np.asarray(ref.ok, bool)
+        fo = r["from_origin" + tag]
+        assert np.isnan(fo[~ok]).all() and (np.abs(fo[ok] - q[ok] / S) <= 3 * n_pad * 2.0 ** -53 * q[ok] / S).all(), (group, tag)
+        return st
+    r = fresh.result["msd_small_ortho_8"]
+    assert r["raised"] is None and np.array_equal(r["st"], msd_state(r, "", "small", "xyz", True, frames[0:8], boxes[0:8], 8)) and not r["st"].any()
+    assert np.abs(r["disp"]).max() < 0.1                                         # (unwrapped: no jump of a box length is left)
+    again = fresh.result["msd_appended_in_three"]                                # however the frames were cut into calls
+    assert again["raised"] is None and all(bits(again[label], r[label]) for label in ("disp", "from_origin", "msd", "pairs", "msd3", "pairs3", "st"))
+    r = fresh.result["msd_masked_tric_8"]
+    assert r["raised"] is None and np.array_equal(r["st"], msd_state(r, "", "masked", "xy", False, frames[8:16], boxes[8:16], 8)) and not r["st"].any()
+    assert not r["disp"][..., 2].any() and np.abs(r["disp"]).max() > 1.0          # (as the positions stand: the jumps are in)
+    r = fresh.result["fail_msd_nobox"]
+    st = msd_state(r, "", "small", "xyz", True, frames[0:4], [boxes[0], boxes[1], None, boxes[3]], 4)
+    assert r["raised"] is None and np.array_equal(r["st"], st) and st.tolist() == [0, 0, E_NO_BOX, 0] and not r["disp"][2].any()
+    r = fresh.result["fail_msd_capacity"]
+    assert r["raised"] is None and r["st"].tolist() == [0] * 16 + [HW.LIB.E_INVALID_ARG] and r["refused"][0] == "DeviceError" and r["n_frames"] == 16
+    msd_state(r, "_before", "small", "xyz", True, frames[0:8] + frames[0:8], boxes[0:8] + boxes[0:8], 16)
+    for label in ("disp", "from_origin", "msd", "pairs", "msd3", "pairs3"):      # the refused call changed nothing
+        assert bits(r[label], r[label + "_before"]), label
+
+    # -- VectorCorrelation (test_gpu_vcorr.py): a vector inside the cell is the panel rule bit for bit, one that straddles it within the
+    #    derived bound of the f64 minimum image; correlate_each is the chains over the device's own panel bit for bit, correlate within
+    #    vcorr_ref.sum_bound of the long-double direct sum
+    U = 2.0 ** -53
+    pairs_t = t["pairs"].astype(np.int64)
+    def vcorr_state(r, fr, bx):
+        ref = vcorr_ref.Panels(pairs_t, unit=True, pbc=True)
+        st, bad = ref.append(fr, bx)
+        x, ok, V, n_pad = r["vectors"], np.asarray(ref.ok, bool), len(pairs_t), r["n_pad"]
+        assert n_pad % 64 == 0 and 0 <= n_pad - V < 64 and x.shape == (len(fr), V, 3)
+        coord = max(float(np.nanmax(np.abs(f))) for f in fr)
+        for k in range(len(fr)):
+            if not ok[k]:
+                assert not x[k].any()
+                continue
+            raw = fr[k][pairs_t[:, 1]].astype(np.float64) - fr[k][pairs_t[:, 0]].astype(np.float64)
+            d = vcorr_ref.vectors64(fr[k], pairs_t, bx[k], unit=False)
+            straddle = np.abs(raw - d).max(1) > 0
+            assert bits(x[k][~straddle], ref.rows[k][~straddle]), k
+            shortest = float(np.sqrt((d * d).sum(1)).min())
+            eps = vcorr_ref.unit_error(coord, shortest, steps=5.0, size=2.0 * coord, stored=False)
+            assert np.abs(x[k].astype(np.float64) - vcorr_ref.vectors64(fr[k], pairs_t, bx[k])).max() <= eps, k
+        assert bits(r["each1"], vcorr_ref.each(x, ok, 1, 4)) and bits(r["each2"], vcorr_ref.each(vcorr_ref.rank2(x), ok, 2, 4))
+        want_pairs = vcorr_ref.pair_counts(ok)
+        assert np.array_equal(r["pairs"], want_pairs)
+        den, have = want_pairs.astype(np.float64) * V, want_pairs > 0
+        for rank, got, panel in ((1, r["c1"], x), (2, r["c2"], vcorr_ref.rank2(x))):
+            S, A = vcorr_ref.direct(panel, ok)
+            want = vcorr_ref.close(np.asarray(S, np.float64), den, rank)
+            assert np.array_equal(np.isnan(got), ~have)
+            bound = vcorr_ref.sum_bound(A, want_pairs, panel.shape[2] * n_pad)[have] / den[have] * (1.5 if rank == 2 else 1.0) + 4 * U * (np.abs(want[have]) + 1.0)
+            assert (np.abs(got[have] - want[have]) <= bound).all(), rank
+        return st
+    for name, lo in (("vcorr_ortho_8", 0), ("vcorr_tric_8", 8)):
+        r = fresh.result[name]
+        assert r["raised"] is None and np.array_equal(r["st"], vcorr_state(r, frames[lo:lo + 8], boxes[lo:lo + 8])) and not r["st"].any(), name
+        assert abs(r["c1"][0] - 1.0) <= 9 * vcorr_ref.EPS32 and abs(r["c2"][0] - 1.0) <= 35 * vcorr_ref.EPS32
+    r = fresh.result["fail_vcorr_nan"]
+    st = vcorr_state(r, frames[0:2] + [HW.nan_frame(2, HW.NAN_SERIES), frames[3]], boxes[0:4])
+    assert r["raised"] is None and np.array_equal(r["st"], st) and st.tolist() == [0, 0, E_NO_POSITION, 0] and r["pairs"].tolist() == [3, 1, 1, 1]
+
+    # -- Internals (test_gpu_internals.py): the values within internals_ref.bounds of the f64 values, the accumulator the restatement's
+    #    sums over the rows `values` returns, bit for bit
+    tuples = {"distance": t["pairs"], "angle": t["angles"], "dihedral": t["dihedrals"]}
+    def values(which, v, k, pos, box):
+        bound = internals_ref.bounds(which, pos, tuples[which], box)
+        err = internals_ref.error(which, v[k], internals_ref.values64(which, pos, tuples[which], box))
+        assert bound.max() < 1e-3 and (err <= bound).all(), (which, k, float((err / bound).max()))
+    for name, which, nf in (("internals_distance_16", "distance", 16), ("internals_angle_16", "angle", 16), ("internals_dihedral_8", "dihedral", 8)):
+        r = fresh.result[name]
+        assert r["raised"] is None and not r["st"].any() and r["v"].shape == (nf, len(tuples[which])) and r["v"].dtype == F, name
+        for k in range(nf):
+            values(which, r["v"], k, frames[k], boxes[k])
+    def accumulated(r, which, rows):
+        ref = internals_ref.State(which, len(tuples[which])).add(rows)
+        assert r["n_" + which] == ref.n and bits(r["origin_" + which], ref.o) and bits(r["sum_" + which], ref.s) and bits(r["sq_" + which], ref.q), which
+        mean, var = ref.close()
+        assert np.abs(r["mean_" + which] - mean).max() <= 1e-12 and np.abs(r["var_" + which] - var).max() <= 1e-12, which
+    r = fresh.result["internals_accumulate_16"]
+    assert r["raised"] is None and not r["st"].any()
+    accumulated(r, "angle", fresh.result["internals_angle_16"]["v"])
+    assert bits(r["v_dihedral"][:8], fresh.result["internals_dihedral_8"]["v"])
+    for k in range(8, 16):
+        values("dihedral", r["v_dihedral"], k, frames[k], boxes[k])
+    accumulated(r, "dihedral", r["v_dihedral"])
+    r = fresh.result["fail_internals_nan"]
+    assert r["raised"] is None and r["st"].tolist() == r["st_values"].tolist() == [0, E_NO_POSITION, 0] and np.isnan(r["v"][1]).all() and r["n_dihedral"] == 2
+    for k, f in ((0, 4), (2, 6)):
+        values("dihedral", r["v"], k, frames[f], boxes[f])
+        assert bits(r["v"][k], fresh.result["internals_dihedral_8"]["v"][f])
+    accumulated(r, "dihedral", r["v"])                                           # the failed frame is counted for no tuple
+
+    # -- RMSDPanel: the oracle's matrix within 1e-5 nm (rmsd_matrix_ref.TOL, test_gpu_rmsd_matrix.py), the forms of one matrix bit for bit
+    m = h["masses"]
+    def matrix(got, group, rows, cols, what):
+        idx = h["groups"][group].astype(np.uint64)
+        want = rmsd_matrix_ref.oracle_matrix([frames[f] for f in rows], [h["boxes"][f] for f in rows], [frames[f] for f in cols], [h["boxes"][f] for f in cols], m, idx)
+        assert got.shape == want.shape and got.dtype == F and np.abs(got - want).max() <= rmsd_matrix_ref.TOL, (what, float(np.abs(got - want).max()))
+    r = fresh.result["panel_big_16"]
+    assert r["raised"] is None and not r["st"].any() and not r["status"].any() and np.array_equal(r["m"], r["m"].T)
+    matrix(r["m"], "big", range(16), range(16), "panel_big_16")
+    r2 = fresh.result["panel_big_small_cols"]
+    assert r2["raised"] is None and not r2["st"].any() and rmsd_matrix_ref.same_bits(r2["m_big"], r["m"][8:, 8:])
+    assert r2["m"].shape == (16, 8) and rmsd_matrix_ref.same_bits(r2["m"], r2["m_again"])
+    matrix(r2["m"], "small", range(16), range(4, 12), "small rows and columns")
+    matrix(r2["m_t"], "small", range(4, 12), range(16), "small columns and rows")
+    assert r2["refused"][:2] == ("RMSDError", "InconsistentGroup") and r2["refused"][2][1:] == (len(h["groups"]["small"]), len(h["groups"]["big"]))
+    r3 = fresh.result["panel_device"]
+    assert r3["raised"] is None and not r3["st"].any() and r3["shape"] == (8, 8) and rmsd_matrix_ref.same_bits(r3["m"], r["m"][8:, 8:])
+    r = fresh.result["fail_panel_nan"]
+    assert r["raised"] is None and r["st"].tolist() == r["status"].tolist() == [0, E_NO_POSITION, 0] and r["len"] == 3
+    assert np.isnan(r["m"][1]).all() and np.isnan(r["m"][:, 1]).all()            # the failed frame took a row, and its entries are NaN
+    assert rmsd_matrix_ref.same_bits(r["m"][np.ix_([0, 2], [0, 2])], fresh.result["panel_big_16"]["m"][np.ix_([2, 4], [2, 4])])
+    r = fresh.result["fail_panel_masses"]
+    assert r["raised"] is None and r["st"].tolist() == [HW.LIB.E_INVALID_ARG, 0, 0, 0, 0] and r["len_refused"] == 0 and not r["status"].any()
+    assert r["refused"][0] == "DeviceError" and "the masses of its atoms have changed" in str(r["refused"][2])
+    assert rmsd_matrix_ref.same_bits(r["m"], fresh.result["panel_big_16"]["m"][:4, :4])
+
+
 def _check_io(G, fresh, h, aux, tmp):
     # the writers: the host encoder's bytes (test_gpu_xtc_encoder_device.py)
     for count, repeat in ((4, 5), (12, 2)):
@@ -510,7 +766,7 @@ def test_fresh_results_are_right(G, fresh, tmp_path):
     h = HW.host_world()
     aux = HW.make_world(G, tmp_path)
     checks = [lambda: _check_centres(fresh, h), lambda: _check_moves(fresh, h), lambda: _check_rmsd(fresh, h), lambda: _check_pairs(G, fresh, h, aux),
-              lambda: _check_topology(G, fresh, h), lambda: _check_io(G, fresh, h, aux, tmp_path), lambda: _check_failures(fresh, h)]
+              lambda: _check_topology(G, fresh, h), lambda: _check_gyration(fresh, h), lambda: _check_series(G, fresh, h), lambda: _check_io(G, fresh, h, aux, tmp_path), lambda: _check_failures(fresh, h)]
     failed = []
     try:
         for k, check in enumerate(checks):                   # every family is checked, whatever the ones before it found
