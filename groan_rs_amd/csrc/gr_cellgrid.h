@@ -13,10 +13,11 @@
 //   k_cg_starts   first sorted position of every cell (binary search per cell)
 //   k_cg_pairs<false>  one lane per group-1 atom: count its pairs                 -> rocprim::exclusive_scan
 //   k_cg_pairs<true>   the same walk, writing (i, j, d) at the atom's offset, then the lane sorts its own short segment by j
+//
+// GEOMETRY (GrCellGrid, gr_cellgrid_make, gr_cg_cell_of; no HIP in this half: tests/cpp/test_cellgrid.cpp compiles it with the host
+// compiler and walks every cell border) comes first, the kernels follow under __HIPCC__.
 #pragma once
-#include <rocprim/rocprim.hpp>
 #include "gr_math.h"
-#include "gr_kernels.h"
 
 struct GrCellGrid {
     uint32_t nc[3];          // cells per axis (orthorhombic: along x, y, z; triclinic: along the box vectors a, b, c)
@@ -25,16 +26,38 @@ struct GrCellGrid {
     int tric;
 };
 
-// cells per axis for a cut-off: the cell is at least (1 + 1e-5) x cutoff thick so that rounding at a cell border can never
-// put two atoms within the cut-off two cells apart (the reference bins with the bare cut-off; the pruned set is the same).
+// cells per axis for a cut-off (the reference bins with the bare cut-off; the pruned set is the same).  The grid only prunes when two
+// atoms whose COMPUTED distance is within the cut-off can never sit two cells apart, so a cell is thicker than the cut-off by everything
+// that rounding can put between the distance and the difference of the two cell coordinates.  Per axis, with u = L x 2^-23 (>= ulp(L)):
+//   wrap      the cell is taken from the WRAPPED coordinate, the distance from the positions as they are.  Within one box length of the
+//             cell, and beyond GR_LOOP_TURNS, the wrap is one rounded t - k L: u / 2 per atom.  In between gr_wrap_value runs the
+//             reference's loop and rounds once per turn, each time by at most half an ulp of what is left: at most
+//             (16 + 15 + ... + 1) u / 2 = 68 u per atom
+//   distance  fl(x_j - x_i) is off by |x_j - x_i| / L x u / 2.  Its minimum image is one rounded d - k L, u / 4, within one turn and
+//             beyond GR_EXACT_TURNS = 20; in between gr_minimg_value runs the reference's loop: (19.5 + 18.5 + ... + 0.5) u / 2 = 100 u
+//   binning   x * inv_cell with inv_cell = fl(n / L): two roundings of a value below n, n x 2^-23 cells = u, per atom
+//   the rest  fl(L / cs), cs itself and the magnitude of the distance are relative roundings of 2^-24 each: the factor 1.00001 covers them
+// Two atoms at most 20 box lengths apart: 68 + 68 + 10 + 100 + 2 = 248 u.  Farther apart the minimum image is the closed form and
+// fl(x_j - x_i) leads: 138 u + |x_j - x_i| / L x u / 2 stays below 256 u up to 236 box lengths.  GR_CG_SLACK = 2^-15 = 256 x 2^-23 per
+// unit of L is that bound (a power of two: cutoff + GR_CG_SLACK x L rounds once whether or not the compiler fuses it), and the reason why
+// GR_EXACT_TURNS is not larger: a 21st turn of the loop would take the first sum to 259 u.
+// The slack had been the factor alone, 1e-5 x cutoff, which u / 2 overtakes in boxes of a few tens of nm: an atom outside the cell was
+// then binned two cells from a partner exactly at the cut-off.  tests/cpp/test_cellgrid.cpp walks every cell border of several thousand
+// boxes with the floats around it, moved by -L, +L, -2 L and +17 L, and finds no pair within the cut-off two cells apart (it finds them
+// with the old rule).  In triclinic cells L is the sum of the box matrix's magnitudes, which bounds every coordinate of the brick: the
+// wrap's three shifts, the fractional coordinates and the table search round at that scale (no loop runs there).
 // Triclinic boxes (extension; the reference's CellGrid needs an orthogonal box, cellgrid.rs:411-430): the grid lives in
 // FRACTIONAL coordinates -- nc_a slabs between lattice planes parallel to (b, c), and so on -- and a slab's thickness is the
 // cell's perpendicular height over nc: h_a = V / |b x c|, h_b = V / |c x a|, h_c = V / |a x b| = cz.  Two atoms whose
 // minimum-image distance is within the cut-off then sit in the same or in periodically adjacent slabs along every axis, so
 // the 27-cell walk of the orthorhombic grid finds them.
+#define GR_CG_SLACK 0x1p-15f
+// the sum above in quarters of u, from the constants themselves: two wraps of GR_LOOP_TURNS turns, fl(x_j - x_i) and the minimum image's
+// loop over GR_EXACT_TURNS box lengths, two binnings -- whoever lengthens a loop has to widen the slack with it
+static_assert(2 * GR_LOOP_TURNS * (GR_LOOP_TURNS + 1) + 2 * GR_EXACT_TURNS + GR_EXACT_TURNS * GR_EXACT_TURNS + 8 <= 4.0f * GR_CG_SLACK * 0x1p23f,
+              "GR_CG_SLACK does not cover the roundings of GR_LOOP_TURNS / GR_EXACT_TURNS turns");
 static inline GrCellGrid gr_cellgrid_make(const GrBox &b, float cutoff) {
     GrCellGrid g;
-    const float cs = cutoff * 1.00001f;
     g.ncells = 1;
     g.tric = b.ortho ? 0 : 1;
     double h[3] = { b.ax, b.by, b.cz };
@@ -45,7 +68,9 @@ static inline GrCellGrid gr_cellgrid_make(const GrBox &b, float cutoff) {
         h[1] = V / (ax * sqrt(cz * cz + cy * cy));                              // |c x a| = ax sqrt(cy^2 + cz^2)
         h[2] = cz;
     }
+    const float scale = fabsf(b.ax) + fabsf(b.by) + fabsf(b.cz) + fabsf(b.bx) + fabsf(b.cx) + fabsf(b.cy);
     for (int a = 0; a < 3; ++a) {
+        const float cs = (cutoff + GR_CG_SLACK * (g.tric ? scale : (float)h[a])) * 1.00001f;
         float n = floorf((float)h[a] / cs);
         if (!(n >= 1.0f)) n = 1.0f;
         if (n > 1024.0f) n = 1024.0f;    // bounded table: more cells than this only make the lists shorter than one atom
@@ -56,7 +81,7 @@ static inline GrCellGrid gr_cellgrid_make(const GrBox &b, float cutoff) {
     return g;
 }
 
-__device__ __forceinline__ void gr_cg_cell_of(float x, float y, float z, const GrBox &box, const GrCellGrid &g, uint32_t (&c)[3]) {
+GR_HD void gr_cg_cell_of(float x, float y, float z, const GrBox &box, const GrCellGrid &g, uint32_t (&c)[3]) {
     gr_wrap(x, y, z, box);                                       // pos.wrap(simbox), cellgrid.rs:463
     float p[3] = { x, y, z };
     if (g.tric) {   // fractional coordinates of the wrapped position, taken modulo 1 (the brick is not the parallelepiped)
@@ -70,6 +95,10 @@ __device__ __forceinline__ void gr_cg_cell_of(float x, float y, float z, const G
         c[a] = (uint32_t)k % g.nc[a];                            // pos == L lands in cell 0 (rem_euclid, :472-474)
     }
 }
+
+#if defined(__HIPCC__)
+#include <rocprim/rocprim.hpp>
+#include "gr_kernels.h"
 
 __global__ __launch_bounds__(256) void k_cg_assign(const float *__restrict__ xyz, GrSel sel, const GrBox box, const GrCellGrid g,
                                                    uint32_t *__restrict__ keys, uint32_t *__restrict__ vals, uint32_t *__restrict__ bad) {
@@ -141,3 +170,5 @@ __global__ __launch_bounds__(256) void k_cg_pairs(const float *__restrict__ xyz,
         out_j[base + b] = vj; out_d[base + b] = vd;
     }
 }
+
+#endif   // __HIPCC__

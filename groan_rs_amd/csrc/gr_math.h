@@ -61,7 +61,7 @@ struct GrBox {
 // t - k L is bit-identical to the reference's loop.  Beyond one turn the loop rounds once per turn: gr_wrap_value /
 // gr_minimg_value then RUN the loop for up to GR_LOOP_TURNS turns (bit-identical again) and keep the closed form only for
 // coordinates farther away than that (an ulp from the reference's value) -- a far-away, infinite or NaN coordinate cannot
-// stall a wavefront.
+// stall a wavefront.  (The distances that decide membership run the minimum image's loop for GR_EXACT_TURNS turns, below.)
 GR_HD float gr_wrap_k(float t, float L, float iL) {
     float k = floorf(t * iL);
     float r = fmaf(-k, L, t);
@@ -92,12 +92,18 @@ GR_HD float gr_minimg_k(float d, float L, float iL, float h) {
     k += (r < -h) ? -1.0f : 0.0f;
     return k;
 }
+// TURNS: how far out the loop is run.  GR_EXACT_TURNS is for the distances that are COMPARED with a threshold (gr_distance<.., true>:
+// shapes, cut-off pairs): there an ulp of the far coordinate decides membership (6e-5 nm at 17 turns of a 41 nm box), so the loop is
+// followed farther out.  Every turn rounds, and the cell grid's slack has to cover what the turns add up to: 20 is the most that
+// GR_CG_SLACK covers (gr_cellgrid.h).
+#define GR_EXACT_TURNS 20
+template <int TURNS = GR_LOOP_TURNS>
 GR_HD float gr_minimg_value(float d, float L, float iL, float h) {
     const float k = gr_minimg_k(d, L, iL, h);
-    if (fabsf(k) <= 1.0f || !(fabsf(k) <= (float)GR_LOOP_TURNS)) return fmaf(-k, L, d);
+    if (fabsf(k) <= 1.0f || !(fabsf(k) <= (float)TURNS)) return fmaf(-k, L, d);
     float w = d;
-    for (int it = 0; it < GR_LOOP_TURNS + 2 && w > h; ++it) w -= L;
-    for (int it = 0; it < GR_LOOP_TURNS + 2 && w < -h; ++it) w += L;
+    for (int it = 0; it < TURNS + 2 && w > h; ++it) w -= L;
+    for (int it = 0; it < TURNS + 2 && w < -h; ++it) w += L;
     return w;
 }
 GR_HD float gr_min_image(float dx, float L) {
@@ -241,9 +247,10 @@ GR_HD float gr_distance(float ax_, float ay_, float az_, float px, float py, flo
     float dx = ax_ - px, dy = ay_ - py, dz = az_ - pz;
     if (b.ortho) {
         // only the requested components are min-imaged, exactly as vector3d.rs:458-486
-        const float mx = gr_minimg_value(dx, b.ax, b.iax, b.ax / 2.0f);
-        const float my = gr_minimg_value(dy, b.by, b.iby, b.by / 2.0f);
-        const float mz = gr_minimg_value(dz, b.cz, b.icz, b.cz / 2.0f);
+        constexpr int TURNS = EXACT ? GR_EXACT_TURNS : GR_LOOP_TURNS;
+        const float mx = gr_minimg_value<TURNS>(dx, b.ax, b.iax, b.ax / 2.0f);
+        const float my = gr_minimg_value<TURNS>(dy, b.by, b.iby, b.by / 2.0f);
+        const float mz = gr_minimg_value<TURNS>(dz, b.cz, b.icz, b.cz / 2.0f);
         switch (dim) {
         case 1: return mx;
         case 2: return my;

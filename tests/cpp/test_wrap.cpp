@@ -46,6 +46,10 @@ int main() {
             const bool one = std::fabs(t) <= 15.0f * L;
             ++n;
             if (one ? bits(wm) != bits(gm) : (std::fabs(wm - gm) > tol && std::fabs(std::fabs(wm - gm) - L) > tol)) { if (bad++ < 20) printf("min_image L=%g d=%.9g: loop %.9g closed %.9g\n", L, t, wm, gm); }
+            // the minimum image of the distances that are compared with a threshold follows the loop up to GR_EXACT_TURNS turns
+            const float ge = gr_minimg_value<GR_EXACT_TURNS>(t, L, 1.0f / L, L / 2.0f);
+            ++n;
+            if (std::fabs(t) <= 19.0f * L && bits(wm) != bits(ge)) { if (bad++ < 20) printf("min_image (exact) L=%g d=%.9g: loop %.9g got %.9g\n", L, t, wm, ge); }
         }
     }
     printf("%ld comparisons, %ld mismatches\n", n, bad);
